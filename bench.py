@@ -13,7 +13,11 @@ per GPU) solves its own pair every step: weak scaling, no data-path collective.
 torch.distributed (nccl = RCCL) is used only for the start/stop barrier and the
 max-over-ranks reduction of the elapsed time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with
+A plain run sets up, warms up, times --steps steps, writes the last timed step's flow with
+--dump-outputs DIR, and prints the line; the fields below are null in it.  --full measures
+them after the timed steps, each in runs of its own.
+
+Prints ONE JSON line on rank 0; under --full it carries
   roofline: dominant kernel class = the iteration passes (k_iterate_roll, k_iterate_tb
             and k_warp_iter, warpBackward fused into each warp's first pass).
             achieved = the bytes those launches move (the engine's live per-launch
@@ -153,6 +157,21 @@ def parse():
     ap.add_argument("--warps", type=int, default=None)
     ap.add_argument("--iterations", type=int, default=300)
     ap.add_argument("--epsilon", type=float, default=0.01)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline "
+                         "figure: one pair alone with and without per-launch HIP events "
+                         "(roofline, pair_breakdown_ms, single_pair_ms), the other arithmetic "
+                         "modes (math_modes), the production ROI strips (production_strips) and "
+                         "the CPU baseline (cpu_baseline); each has its own --no-... switch.  "
+                         "Without --full a run sets up, warms up, times the steps and prints "
+                         "the line, with those fields null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="pair / strips: after the timed steps write the flow the last timed "
+                         "step left in each in-flight slot's output buffers to "
+                         "DIR/rank<r>_slot<j>_{u,v}.npy (float32) and the step's iteration "
+                         "counts to DIR/rank<r>_iterations.npy (float64); above 48 MB in all, "
+                         "the same seeded sample of every array's elements instead of all of "
+                         "them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--fast-math", type=int, default=0, choices=(0, 1, 2), nargs="?", const=1,
                     help="headline arithmetic mode (tvl1_params.fast_math): 0 = IEEE, bit-identical "
@@ -196,6 +215,10 @@ def parse():
     # `torchrun --nproc-per-node N bench.py` without --gpus: the launcher's WORLD_SIZE (an
     # explicit --gpus that disagrees with it stays an error in main())
     args.gpus_explicit = args.gpus is not None
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload == "stack":
+        ap.error("--dump-outputs: the stack workload writes its flows with --dump")
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     geo = (3072, 100, 10, 5) if args.workload == "strips" else (6144, 4096, 5, 30)
@@ -257,6 +280,30 @@ def rank_records(dist, local_rank, pairs, iterations, elapsed):
     out = [None] * dist.get_world_size()
     dist.all_gather_object(out, rec)
     return out
+
+
+DUMP_BUDGET = 48 << 20   # bytes of flow written by --dump-outputs (all arrays of one rank)
+
+
+def dump_outputs(d, rank, flows, iterations):
+    """--dump-outputs: what the last timed step computed on this rank.  flows: one (u, v) pair
+    of device tensors per in-flight slot (the buffers the solve wrote); iterations: the step's
+    iteration counts.  Whole arrays when they fit DUMP_BUDGET, else the same sample of every
+    array's flattened elements (indices from a fixed seed, ascending), so two runs with the
+    same arguments write the same elements."""
+    import numpy as np
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    n = flows[0][0].numel()
+    keep = DUMP_BUDGET // (4 * 2 * len(flows))
+    idx = None
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(n, size=keep, replace=False))
+    for j, uv in enumerate(flows):
+        for name, t in zip("uv", uv):
+            a = t.detach().cpu().numpy().astype(np.float32, copy=False)
+            np.save(d / f"rank{rank}_slot{j}_{name}.npy", a if idx is None else a.reshape(-1)[idx])
+    np.save(d / f"rank{rank}_iterations.npy", np.asarray(iterations, dtype=np.float64))
 
 
 _NATIVE_ORACLE = None
@@ -534,18 +581,23 @@ def run_strips(args, rank, world, local_rank, dist, standalone=True):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     iters = 0
+    last = []
     for _ in range(args.steps):
-        for st in step():
+        last = step()
+        for st in last:
             iters += sum(s["iterations_total"] for s in st)
     torch.cuda.synchronize(dev)
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ranks = rank_records(dist, local_rank, args.steps * F * B, iters, elapsed)
-    # one batch alone on the GPU after the timed steps, with HIP events around every launch
-    # (tvl1_set_profiling): the batched iteration class's roofline
+    if args.dump_outputs and standalone:
+        dump_outputs(args.dump_outputs, rank, [(sl["u"], sl["v"]) for sl in slots],
+                     [s["iterations_total"] for b in last for s in b])
+    # --full: one batch alone on the GPU after the timed steps, with HIP events around every
+    # launch (tvl1_set_profiling): the batched iteration class's roofline
     roof = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         slots[0]["eng"].set_profiling(True)
         s0 = solve(slots[0])[0]
         slots[0]["eng"].set_profiling(False)
@@ -572,7 +624,7 @@ def run_strips(args, rank, world, local_rank, dist, standalone=True):
     solves = world * args.steps * F * B
     value = solves / elapsed
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import checker   # cpu_baseline leg only
         st0 = slots[0]["stack"]
         a, c = st0[0].cpu().numpy(), st0[1].cpu().numpy()
@@ -721,8 +773,16 @@ def main():
     F = max(1, args.inflight)
     dev = torch.device("cuda", local_rank)
     slots = []
+    # synth.gen_pair(W, H, seed, z) for every slot, with the base texture and slice 0 (the
+    # same for every z) made once and the slices made side by side (numpy and scipy release
+    # the GIL in them): the same bytes in a fifth of the time
+    from concurrent.futures import ThreadPoolExecutor
+    base = synth.base_texture(W, H, 0x5EED)
+    with ThreadPoolExecutor(max_workers=F + 1) as tp:
+        I0h, *I1s = tp.map(lambda z: synth.make_slice(base, z, 0x5EED),
+                           [0] + [1 + rank * F + j for j in range(F)])
     for j in range(F):
-        I0h, I1h = synth.gen_pair(W, H, seed=0x5EED, z=1 + rank * F + j)
+        I1h = I1s[j]
         eng = capi.Engine(params, device=local_rank)
         eng.set_profiling(False)   # no per-launch events in the timed steps (they cost time)
         # F == 1: torch's current stream; F > 1: each ctx on its own non-blocking stream
@@ -740,7 +800,6 @@ def main():
 
     pool = None
     if F > 1:
-        from concurrent.futures import ThreadPoolExecutor
         pool = ThreadPoolExecutor(max_workers=F)   # ctypes releases the GIL in tvl1_calc
 
     def step():
@@ -776,29 +835,35 @@ def main():
     ranks = rank_records(dist, local_rank, len(stats), sum(s["iterations_total"] for s in stats),
                          own)
     I0h, I1h = slots[0]["I0h"], slots[0]["I1h"]
+    if args.dump_outputs:   # before anything below solves into the same buffers
+        dump_outputs(args.dump_outputs, rank, [(sl["u"], sl["v"]) for sl in slots],
+                     [s["iterations_total"] for s in stats[-F:]])
+    # everything from here to the line is --full's: measurements beside the headline figure
     # one pair alone on the GPU, twice (not timed): with HIP events around every launch for
     # clean per-kernel-class durations (the roofline; no interleaving with other pairs), then
     # without them for the wall time -- the events themselves cost ~2.7 ms per C2 pair
     iso = None
     single_pair_instr_ms = None
-    if not args.no_kernel_timing:
+    single_pair_ms = None
+    if args.full and not args.no_kernel_timing:
         slots[0]["eng"].set_profiling(True)
         t_iso = time.perf_counter()
         iso = solve(slots[0])
         torch.cuda.synchronize(dev)
         single_pair_instr_ms = 1e3 * (time.perf_counter() - t_iso)
         slots[0]["eng"].set_profiling(False)
-    t_iso = time.perf_counter()
-    solve(slots[0])
-    torch.cuda.synchronize(dev)
-    single_pair_ms = 1e3 * (time.perf_counter() - t_iso)
+    if args.full:
+        t_iso = time.perf_counter()
+        solve(slots[0])
+        torch.cuda.synchronize(dev)
+        single_pair_ms = 1e3 * (time.perf_counter() - t_iso)
 
     # secondary measurement in the other math mode (same pairs, same K): the IEEE run is
     # the headline unless --fast-math; its flow is the reference for the EPE figures
     # the other arithmetic modes on the same pairs and K: pairs/s and the
     # per-pixel EPE of pair 0 against the headline run's flow -- the tolerance table
     modes = None
-    if not args.no_fast_math_line:
+    if args.full and not args.no_fast_math_line:
         u_ref, v_ref = slots[0]["u"].clone(), slots[0]["v"].clone()
         modes = {}
         names = {0: "ieee", 1: "fast", 2: "fma"}
@@ -832,7 +897,7 @@ def main():
 
     # the production workload beside the C2 headline, every rank taking part
     strips = None
-    if not args.no_strips_line and args.profile == 0:
+    if args.full and not args.no_strips_line and args.profile == 0:
         for sl in slots:
             sl["eng"].close()
         strips = strips_line(args, rank, world, local_rank, dist)
@@ -862,7 +927,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 3),
-        "single_pair_ms": round(single_pair_ms, 3),
+        "single_pair_ms": None if single_pair_ms is None else round(single_pair_ms, 3),
         "single_pair_ms_with_events": None if single_pair_instr_ms is None else round(single_pair_instr_ms, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -906,7 +971,7 @@ def main():
         # per rank: device (PCI id), pairs solved, own elapsed time of the timed steps
         "ranks": ranks,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(I0h, I1h, params, args.cpu_sample)
     print(json.dumps(out), flush=True)
     if dist:

@@ -82,11 +82,11 @@ def test_plain_launch_runs_n_ranks(built, tmp_path):
 
 def test_plain_launch_default_pair_line(built):
     """The driver's multi-GPU command as written (`bench.py --gpus N --steps K --warmup W`, no
-    launcher, the default pair workload with its extra lines): 2 ranks (gloo, on the one GPU),
-    every collective of the math-mode and production-strip legs reached by both ranks, one
-    JSON line from rank 0 claiming both GPUs, no CPU baseline above one GPU."""
+    launcher, the default pair workload with --full's extra lines): 2 ranks (gloo, on the one
+    GPU), every collective of the math-mode and production-strip legs reached by both ranks,
+    one JSON line from rank 0 claiming both GPUs, no CPU baseline above one GPU."""
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--width", "320", "--height", "240", "--inflight", "2"]
+           "--width", "320", "--height", "240", "--inflight", "2", "--full"]
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BENCH_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")

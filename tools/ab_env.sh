@@ -9,7 +9,7 @@ for i in $(seq 1 "$rounds"); do
   for setting in "$@"; do
     j=$((j + 1))
     out=gpurun_out/ab_env_${j}_$i
-    env $setting timeout -k 10 150 python bench.py --no-strips-line --no-fast-math-line --no-cpu-baseline \
+    env $setting timeout -k 10 150 python bench.py --full --no-strips-line --no-fast-math-line --no-cpu-baseline \
       $BENCH_FLAGS > $out.json 2> $out.err || exit $?
     python - "$out.json" "$setting" <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ set -o pipefail
 mkdir -p gpurun_out
 for i in 1 2; do
   for sp in 1 0; do
-    TVL1_SPEC=$sp timeout -k 10 150 python bench.py --no-strips-line --no-fast-math-line --no-cpu-baseline \
+    TVL1_SPEC=$sp timeout -k 10 150 python bench.py --full --no-strips-line --no-fast-math-line --no-cpu-baseline \
       > gpurun_out/ab_spec_${sp}_$i.json 2> gpurun_out/ab_spec_${sp}_$i.err || exit $?
     python - "$sp" "$i" <<'PY'
 import json, sys

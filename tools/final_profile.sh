@@ -7,7 +7,7 @@ set -o pipefail
 tag=${1:-final}
 out=gpurun_out/$tag
 mkdir -p $out
-timeout -k 10 400 python bench.py > $out/bench_c2.json 2> $out/bench_c2.err || { echo BENCH_FAIL; tail -5 $out/bench_c2.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $out/bench_c2.json 2> $out/bench_c2.err || { echo BENCH_FAIL; tail -5 $out/bench_c2.err; exit 1; }
 TVL1_SPEC=0 bash tools/pmc_single.sh ${tag}_pair || exit 1
 python3 tools/pmc_summary.py gpurun_out/prof_${tag}_pair --emit-traffic $out/traffic.json > $out/pmc_summary_single_pair.txt || exit 1
 TVL1_SPEC=0 bash tools/pmc_stall.sh ${tag} || exit 1

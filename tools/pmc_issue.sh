@@ -13,10 +13,10 @@ tag=${1:-issue}; shift
 if [ "$1" = "--strips" ]; then
   shift
   LV="none:1:1"   # every strip level has its own grid size
-  B="bench.py --workload strips --width 3072 --height 100 --nscales 10 --warps 5 --batch 256 --steps 1 --warmup 1 --inflight 1 --no-cpu-baseline $*"
+  B="bench.py --full --workload strips --width 3072 --height 100 --nscales 10 --warps 5 --batch 256 --steps 1 --warmup 1 --inflight 1 --no-cpu-baseline $*"
 else
   LV="k_warp_iter<:5:30"   # C2: 5 levels x 30 warps, one k_warp_iter per warp
-  B="bench.py --steps 1 --warmup 1 --inflight 1 --no-cpu-baseline --no-fast-math-line --no-strips-line $*"
+  B="bench.py --full --steps 1 --warmup 1 --inflight 1 --no-cpu-baseline --no-fast-math-line --no-strips-line $*"
 fi
 out=gpurun_out/issue_$tag      # summaries (merged back)
 raw=/tmp/issue_raw_$tag        # rocprofv3 output (tens of MB: stays on the box)
