@@ -28,7 +28,8 @@
 //     pool, default min(16, cores - 1)), "medianFiltering",
 //     "matches_file", "stats_json", "timing_json" (per-stage host seconds of strip jobs),
 //     "skip_existing", "pinned_host" (page-locked slices and
-//     flows, default off).
+//     flows, default off), "initialFlow" ([dx, dy]: with "useInitialFlow", the pair's ROIs
+//     are solved from that constant flow, tvl1_calc_init).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -135,6 +136,28 @@ bool resolve_features(const Value &im, const Value &args) {
   if (args.isMember("features") && !args["features"].asBool()) return false;
   if (im.get("features", false).asBool() || args.get("features", false).asBool()) return true;
   return false;
+}
+
+// build-only "initialFlow": [dx, dy] (px of the pre-scaled frame, flow from frame0 to frame1),
+// per image or global, honoured only with "useInitialFlow": true: the pair's ROIs are solved
+// by tvl1_calc_init from that constant flow.  "useInitialFlow" alone stays without effect,
+// as in the reference (optflow.cpp:512, never passed to create()).
+struct InitFlow {
+  bool on = false;
+  float dx = 0.f, dy = 0.f;
+};
+const char *const kInitFlowFeatures =
+    "initialFlow cannot be combined with feature alignment (features, a pair without ROIs, or "
+    "frames of different sizes)";
+InitFlow initial_flow_of(const Value &im, const Value &args) {
+  InitFlow f;
+  if (!im.get("useInitialFlow", args.get("useInitialFlow", false).asBool()).asBool()) return f;
+  const Value &v = im.isMember("initialFlow") ? im["initialFlow"] : args["initialFlow"];
+  if (!v.isArray() || v.size() != 2) return f;
+  f.on = true;
+  f.dx = v[0].asFloat();
+  f.dy = v[1].asFloat();
+  return f;
 }
 
 bool file_exists(const std::string &p) {
@@ -514,6 +537,7 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
                    const float *affine, PairResult &res, std::string &err) {
   const int W = r0.width, H = r0.height;
   tvl1_params prm = generate_TV_args(im, args);
+  const InitFlow init = initial_flow_of(im, args);
   if (const tvl1_status s = tvl1_set_params(dc.ctx, &prm); s != TVL1_OK) {
     err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
     return false;
@@ -543,9 +567,29 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
     sv["checks"] = (int64_t)st.checks_total;
     const size_t nw = std::min(warp_iters.size(), (size_t)std::max(0, st.levels) * std::max(1, prm.warps));
     for (size_t k = 0; k < nw; ++k) sv["warp_iterations"][(int)k] = warp_iters[k];
+    if (init.on) {
+      sv["initial_flow"][0] = (double)init.dx;
+      sv["initial_flow"][1] = (double)init.dy;
+    }
     res.stats["solves"].append(sv);
   };
-  tvl1_status s = tvl1_calc(dc.ctx, a, pitch, b, pitch1, W, H, dc.du, dc.dv, fp, &st, dc.stream);
+  tvl1_status s;
+  if (init.on) {
+    // the seed is the flow buffers' own content (tvl1_calc_init's in/out flow): two planes of
+    // the ROI's size filled with the constants
+    uint32_t bx, by;
+    memcpy(&bx, &init.dx, 4);
+    memcpy(&by, &init.dy, 4);
+    if (hipMemsetD32Async((hipDeviceptr_t)dc.du, (int)bx, (size_t)W * H, dc.stream) != hipSuccess ||
+        hipMemsetD32Async((hipDeviceptr_t)dc.dv, (int)by, (size_t)W * H, dc.stream) != hipSuccess) {
+      err = "initial flow fill failed", dc.faulted = true;
+      return false;
+    }
+    s = tvl1_calc_init(dc.ctx, a, pitch, b, pitch1, W, H, dc.du, dc.dv, fp, dc.du, dc.dv, fp, &st,
+                       dc.stream);
+  } else {
+    s = tvl1_calc(dc.ctx, a, pitch, b, pitch1, W, H, dc.du, dc.dv, fp, &st, dc.stream);
+  }
   if (s != TVL1_OK) {
     err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
     return false;
@@ -736,6 +780,12 @@ bool solve_rois(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1_in
   ofio::Image8 f1_aligned;               // frame1 after find_alignment + warpAffine
   const ofio::Image8 *f1p = &f1_in;      // the frame1 the ROIs read: the slice or f1_aligned
   bool features = resolve_features(im, args);
+  // a seeded pair is not pre-aligned: the seed is a flow between the frames as they are
+  const bool seeded = initial_flow_of(im, args).on;
+  if (seeded && features) {
+    err = kInitFlowFeatures;
+    return false;
+  }
   const std::string otype = output_type_of(im, args);
   // cv::Mat affine(cv::Size(3,2), CV_32FC1) (optflow.cpp:319) is uninitialised until
   // find_alignment fills it; the identity stands in for that here.
@@ -793,6 +843,10 @@ bool solve_rois(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1_in
         if (size_differs || (key == "default" && !features))
           fprintf(stderr, "Rows or columns differ between frames no ROI selected, reverting to "
                           "features even though it wasn't selected.\n");
+        if (seeded) {   // (no ROI, or frames of different sizes: the reference aligns these)
+          err = kInitFlowFeatures;
+          return false;
+        }
         if (!align_frame1(dc, f0, *f1p, f1_aligned, im, args, affine, err)) return false;
         f1p = &f1_aligned;
         features = true;
@@ -935,6 +989,14 @@ static int from_file(Value &args, bool plan_only) {
   const size_t n = images.size();
   std::vector<PairResult> results(n);
   std::vector<Value> plans(n);
+  // a config that cannot run as written ends the job before any slice is read
+  auto fail = [](const std::string &what) {
+    fprintf(stderr, "Error: %s\n", what.c_str());
+    return 2;
+  };
+  for (size_t i = 0; i < n; ++i)
+    if (initial_flow_of(images[i], args).on && resolve_features(images[i], args))
+      return fail("pair " + std::to_string(i) + ": " + kInitFlowFeatures);
 
   // build-only: shard pairs over several GPUs (contiguous chunks keep slice reuse)
   std::vector<int> devices;
@@ -1113,6 +1175,10 @@ static int from_file(Value &args, bool plan_only) {
           pl["output_type"] = output_type_of(im, args);
           pl["features"] = resolve_features(im, args);
           pl["strip_batch"] = (bool)batch_ok[i];   // solved in a tvl1_calc_batch chunk
+          if (const InitFlow f0 = initial_flow_of(im, args); f0.on) {   // tvl1_calc_init per ROI
+            pl["initialFlow"][0] = (double)f0.dx;
+            pl["initialFlow"][1] = (double)f0.dy;
+          }
           const tvl1_params tp = generate_TV_args(im, args);
           pl["tv"]["tau"] = tp.tau;
           pl["tv"]["lambda"] = tp.lambda;
@@ -1597,7 +1663,8 @@ static int from_file(Value &args, bool plan_only) {
     roi_bottom = args["rois"].get("bottom", 300).asInt();
     static const char *kProd[] = {"p", "q", "pId", "qId", "pGroupId", "qGroupId", "output_name", "output"};
     for (size_t i = 0; i < n; ++i) {
-      bool ok = images[i].isObject();
+      // a seeded pair's ROIs are solved one by one (tvl1_calc_init)
+      bool ok = images[i].isObject() && !initial_flow_of(images[i], args).on;
       for (auto &k : images[i].memberNames())
         ok = ok && std::find_if(std::begin(kProd), std::end(kProd), [&](const char *x) { return k == x; }) !=
                        std::end(kProd);

@@ -69,6 +69,36 @@ __global__ void kb_resize_down2(const float *__restrict__ a0, const float *__res
   dst[(size_t)y * dp + x] = resize_px<C>(src, sw, sh, sp, x, y, fx, fy);
 }
 
+// [A.2b] k_flow_down for every pair (blockIdx.z = 2 * pair + component).  Pair strides in
+// floats; the first step's source is the caller's seed (sps = 0: one seed for every pair).
+template <bool C>
+__global__ void kb_flow_down(const float *__restrict__ s1, const float *__restrict__ s2, int sw,
+                             int sh, int sp, size_t sps, float *__restrict__ d1,
+                             float *__restrict__ d2, int dw, int dh, int dp, size_t dps, float fx,
+                             float fy, float mul) {
+  const int x = blockIdx.x * 64 + threadIdx.x;
+  const int y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= dw || y >= dh) return;
+  const int b = blockIdx.z >> 1;
+  const float *src = ((blockIdx.z & 1) == 0 ? s1 : s2) + b * sps;
+  float *dst = ((blockIdx.z & 1) == 0 ? d1 : d2) + b * dps;
+  dst[(size_t)y * dp + x] = resize_px<C>(src, sw, sh, sp, x, y, fx, fy) * mul;
+}
+
+// A one-level pyramid takes the seed as it is: the caller's pitched planes into every pair's
+// u set (blockIdx.z = 2 * pair + component; the single-pair solve is a batch of one).
+TVL1_PLAIN __global__ void kb_flow_copy(const float *__restrict__ s1, const float *__restrict__ s2,
+                                        int sp, size_t sps, float *__restrict__ d1,
+                                        float *__restrict__ d2, int W, int H, int dp, size_t dps) {
+  const int x = blockIdx.x * 64 + threadIdx.x;
+  const int y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= W || y >= H) return;
+  const int b = blockIdx.z >> 1;
+  const float *src = ((blockIdx.z & 1) == 0 ? s1 : s2) + b * sps;
+  float *dst = ((blockIdx.z & 1) == 0 ? d1 : d2) + b * dps;
+  dst[(size_t)y * dp + x] = src[(size_t)y * sp + x];
+}
+
 // K5 as k_warp_ring's streaming gather (64-px bands, LDS window ring of I1 / I1x / I1y
 // built from I1) on each selected pair (blockIdx.y = entry of sel).
 struct BatchRing {
@@ -271,7 +301,8 @@ constexpr int kSmallPx = 9000;      // LDS planes of W * H floats: I1 and the th
 
 struct BatchSmall {
   const float *I0, *I1;   // the level's images of pair 0 (pair stride ips)
-  float *u1, *u2;         // u set written (pair stride ps); the level starts from u = 0
+  float *u1, *u2;         // u set written (pair stride ps); the level starts from u = 0, or
+                          // (SEED) from the flow these planes hold
   size_t ips, ps;
   int W, H, P;            // level geometry; P = plane pitch in floats
   int warps, iterations, eps_pos;
@@ -282,7 +313,7 @@ struct BatchSmall {
   BatchSel sel;
 };
 
-template <int FM>
+template <int FM, bool SEED = false>
 __global__ __launch_bounds__(64 * kSmallWaves) void kb_small_level(BatchSmall a) {
   __shared__ float sI1[kSmallPx];
   __shared__ float sC[3][kSmallPx];
@@ -310,6 +341,14 @@ __global__ __launch_bounds__(64 * kSmallWaves) void kb_small_level(BatchSmall a)
   float u1[R], u2[R], p11[R], p12[R], p21[R], p22[R];
 #pragma unroll
   for (int y = 0; y < R; ++y) u1[y] = u2[y] = p11[y] = p12[y] = p21[y] = p22[y] = 0.0f;
+  if constexpr (SEED) {   // the seeded coarsest level [A.2b]: this lane's column of u
+#pragma unroll
+    for (int y = 0; y < R; ++y) {
+      if (y >= H) continue;   // (a fixed trip count: fully unrolled)
+      u1[y] = a.u1[b * a.ps + (size_t)y * P + xs];
+      u2[y] = a.u2[b * a.ps + (size_t)y * P + xs];
+    }
+  }
   if (lane == 63)
     for (int y = 0; y < R; ++y) xp[wv][0][y] = xp[wv][1][y] = 0.0f;
   __syncthreads();

@@ -636,6 +636,13 @@ struct Frames {
   bool f32;
 };
 
+// The initial flow of a solve (tvl1_calc_init): device planes of the frame's
+// size, row pitch and pair stride in floats (stride 0: one seed for every pair of a batch).
+struct Seed {
+  const float *u0, *v0;
+  size_t pitch, stride;
+};
+
 // [A.1] I0f = convertTo(CV_32F, u8 ? 1 : 255) into the level-0 planes
 static void convert_frames(tvl1_ctx *c, const Frames &in, int W, int H, hipStream_t st) {
   if (in.f32)
@@ -790,10 +797,14 @@ struct SolveCount {
   ~SolveCount() { g_solving[d].fetch_sub(1, std::memory_order_relaxed); }
 };
 
-static tvl1_status solve(tvl1_ctx *c, const Frames &in, int W, int H, float *u, float *v,
-                         size_t fpitch, tvl1_stats *stats, hipStream_t st) {
+// seed: the initial flow (tvl1_calc_init), or null for u = 0 at the coarsest level
+static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W, int H, float *u,
+                         float *v, size_t fpitch, tvl1_stats *stats, hipStream_t st) {
   const tvl1_params &prm = c->prm;
-  if (prm.profile == 1) return solve_dualtvl1(c, in, W, H, u, v, fpitch, stats, st);
+  if (prm.profile == 1) {
+    if (seed) return set_err(c, TVL1_EINVAL, "profile 1 takes no initial flow");
+    return solve_dualtvl1(c, in, W, H, u, v, fpitch, stats, st);
+  }
   const SolveCount active(c->device);
   const Geometry &g = c->geo;
   const int L = g.L;
@@ -828,12 +839,44 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, int W, int H, float *u, 
 
   int ui = 0, pi = 0;  // ping-pong indices of the u and p buffer sets
   int cb = 0;          // constants buffer (I1wx, I1wy, rho) of the current warp
-  {                    // u = 0 at the coarsest level (no initial flow)
+  if (!seed) {         // u = 0 at the coarsest level (no initial flow)
     const int s = L - 1;
     const size_t n = (size_t)g.ps[s] * g.hs[s] * sizeof(float);
     HIP_TRY(c, hipMemsetAsync(c->U[ui][0], 0, n, st));
     HIP_TRY(c, hipMemsetAsync(c->U[ui][1], 0, n, st));
     if (gam) HIP_TRY(c, hipMemsetAsync(c->U[ui][2], 0, n, st));
+  } else {
+    // [A.2b] the seed's pyramid: u[s] = resize(u[s-1]) * scaleStep, a chain of rounded levels.
+    // Only its coarsest level reaches the solver (every upsample overwrites the finer one), so
+    // the first step reads the caller's planes and the steps ping-pong between the two u sets;
+    // a one-level pyramid takes the seed as it is.  u3 = 0 at the coarsest level either way.
+    const float fmul = (float)prm.scale_step;
+    tk = prof_begin(c, st);
+    double b = 0.0;
+    if (L == 1) {
+      hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2), kBlk2, 0, st, seed->u0, seed->v0,
+                         (int)seed->pitch, (size_t)0, c->U[ui][0], c->U[ui][1], W, H, g.ps[0],
+                         (size_t)0);
+      b = (double)W * H * 16.0;
+    }
+    for (int s = 1; s < L; ++s) {
+      const float *s1 = s == 1 ? seed->u0 : c->U[ui][0], *s2 = s == 1 ? seed->v0 : c->U[ui][1];
+      const int sp = s == 1 ? (int)seed->pitch : g.ps[s - 1];
+      if (s > 1) ui ^= 1;
+      if (contract_pyr)
+        hipLaunchKernelGGL(k_flow_down<true>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st, s1, s2,
+                           g.ws[s - 1], g.hs[s - 1], sp, c->U[ui][0], c->U[ui][1], g.ws[s],
+                           g.hs[s], g.ps[s], fdown, fdown, fmul);
+      else
+        hipLaunchKernelGGL(k_flow_down<false>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st, s1, s2,
+                           g.ws[s - 1], g.hs[s - 1], sp, c->U[ui][0], c->U[ui][1], g.ws[s],
+                           g.hs[s], g.ps[s], fdown, fdown, fmul);
+      b += (double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8;
+    }
+    prof_end(c, st, tk, 2, b);
+    if (gam)
+      HIP_TRY(c, hipMemsetAsync(c->U[ui][2], 0, (size_t)g.ps[L - 1] * g.hs[L - 1] * sizeof(float), st));
+    HIP_TRY(c, hipGetLastError());
   }
 
   const float l_t = (float)(prm.lambda * prm.theta);
@@ -1600,8 +1643,8 @@ static tvl1_status ensure_batch(tvl1_ctx *c, int W, int H, int n, hipStream_t st
 
 static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size_t pitch0,
                                      size_t stride0, const uint8_t *I1, size_t pitch1,
-                                     size_t stride1, int W, int H, float *u, float *v,
-                                     size_t fpitch, size_t fstride, tvl1_stats *stats,
+                                     size_t stride1, const Seed *seed, int W, int H, float *u,
+                                     float *v, size_t fpitch, size_t fstride, tvl1_stats *stats,
                                      hipStream_t st) {
   const tvl1_params &prm = c->prm;
   const Geometry &g = c->geo;
@@ -1642,9 +1685,39 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
     }
 #undef KB_DOWN
   }
-  // u = 0 at the coarsest level, set 0 of every pair
-  for (int k = 0; k < 2; ++k)
-    HIP_TRY(c, hipMemsetAsync(c->bU[0][k], 0, ps * n * sizeof(float), st));
+  if (!seed) {   // u = 0 at the coarsest level, set 0 of every pair
+    for (int k = 0; k < 2; ++k)
+      HIP_TRY(c, hipMemsetAsync(c->bU[0][k], 0, ps * n * sizeof(float), st));
+  } else {
+    // [A.2b] every pair's seed pyramid (solve()'s chain): the first step reads the caller's
+    // planes, the steps alternate between the u sets and the last one writes set 0
+    const float fmul = (float)prm.scale_step;
+    const size_t tkf = prof_begin(c, st);
+    double fb = 0.0;
+    if (L == 1) {
+      hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2 * n), kBlk2, 0, st, seed->u0, seed->v0,
+                         (int)seed->pitch, seed->stride, c->bU[0][0], c->bU[0][1], W, H, g.ps[0], ps);
+      fb = (double)n * W * H * 16.0;
+    }
+    int set = L & 1;   // L - 1 steps end in set 0
+    for (int s = 1; s < L; ++s, set ^= 1) {
+      const float *s1 = s == 1 ? seed->u0 : c->bU[set ^ 1][0], *s2 = s == 1 ? seed->v0 : c->bU[set ^ 1][1];
+      const int sp = s == 1 ? (int)seed->pitch : g.ps[s - 1];
+      const size_t sps = s == 1 ? seed->stride : ps;
+#define KB_FLOW(C)                                                                             \
+  hipLaunchKernelGGL(kb_flow_down<C>, grid2(g.ws[s], g.hs[s], 2 * n), kBlk2, 0, st, s1, s2,    \
+                     g.ws[s - 1], g.hs[s - 1], sp, sps, c->bU[set][0], c->bU[set][1], g.ws[s], \
+                     g.hs[s], g.ps[s], ps, fdown, fdown, fmul);
+      if (contracts(math)) {
+        KB_FLOW(true)
+      } else {
+        KB_FLOW(false)
+      }
+#undef KB_FLOW
+      fb += (double)n * ((double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8);
+    }
+    prof_end(c, st, tkf, 2, fb);
+  }
   HIP_TRY(c, hipGetLastError());
 
   const float l_t = (float)(prm.lambda * prm.theta);
@@ -1685,8 +1758,8 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
     it.taut_small = taut_small(taut);
     // The coarsest level on chip (kb_small_level, one workgroup per pair: every warp's gather,
     // iterations, residuals and stopping rule without leaving the workgroup) when it fits one
-    // workgroup's registers and LDS; u enters as 0 in set 0 and leaves there, and p is reset
-    // at every level anyway
+    // workgroup's registers and LDS; u enters as 0 (or, seeded, as set 0's planes: <FM, true>)
+    // and leaves in set 0, and p is reset at every level anyway
     const bool small = c->batch_small && s == L - 1 && prm.median_filtering <= 1 &&
                        lw <= 64 * kSmallWaves && lh <= kSmallR && lw * lh <= kSmallPx;
     if (small) {
@@ -1715,8 +1788,11 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
       sm.checks = sm.warp_iters + (size_t)n * prm.warps;
       sm.sel = all;
       const size_t tks = prof_begin(c, st);
-#define KB_SMALL(FM) \
-  hipLaunchKernelGGL((kb_small_level<FM>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm);
+#define KB_SMALL(FM)                                                                               \
+  if (seed)                                                                                       \
+    hipLaunchKernelGGL((kb_small_level<FM, true>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm); \
+  else                                                                                            \
+    hipLaunchKernelGGL((kb_small_level<FM>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm);
       MATH_SWITCH(math, KB_SMALL)
 #undef KB_SMALL
       HIP_TRY(c, hipGetLastError());
@@ -2520,7 +2596,36 @@ tvl1_status tvl1_calc(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8
   HIP_TRY(c, hipSetDevice(c->device));
   s = ensure_geometry(c, W, H, (hipStream_t)stream);
   if (s != TVL1_OK) return s;
-  return solve(c, Frames{I0, I1, pitch0, pitch1, false}, W, H, u, v, fpitch, stats,
+  return solve(c, Frames{I0, I1, pitch0, pitch1, false}, nullptr, W, H, u, v, fpitch, stats,
+               (hipStream_t)stream);
+}
+
+// The seed arguments of the tvl1_calc_*_init calls, checked before anything is launched
+// (and before the ctx: a NULL ctx reports the error through tvl1_last_error(NULL)).
+static tvl1_status check_seed(tvl1_ctx *c, const float *u0, const float *v0, size_t ipitch,
+                              int W) {
+  if (!u0 || !v0) return set_err(c, TVL1_EINVAL, "null initial flow pointer");
+  if (W > 0 && (ipitch < sizeof(float) * (size_t)W || ipitch % sizeof(float) ||
+                ipitch / sizeof(float) > (size_t)INT32_MAX))
+    return set_err(c, TVL1_EINVAL, "initial flow pitch must be >= 4*width and a multiple of 4");
+  if (c && c->prm.profile == 1)
+    return set_err(c, TVL1_EINVAL, "profile 1 takes no initial flow (tvl1_calc_init)");
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_calc_init(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
+                           size_t pitch1, int32_t W, int32_t H, const float *u0, const float *v0,
+                           size_t init_pitch, float *u, float *v, size_t fpitch,
+                           tvl1_stats *stats, void *stream) {
+  tvl1_status s = check_seed(c, u0, v0, init_pitch, W);
+  if (s != TVL1_OK) return s;
+  s = check_call(c, I0, pitch0, I1, pitch1, W, H, u, v, fpitch);
+  if (s != TVL1_OK) return s;
+  HIP_TRY(c, hipSetDevice(c->device));
+  s = ensure_geometry(c, W, H, (hipStream_t)stream);
+  if (s != TVL1_OK) return s;
+  const Seed seed{u0, v0, init_pitch / sizeof(float), 0};
+  return solve(c, Frames{I0, I1, pitch0, pitch1, false}, &seed, W, H, u, v, fpitch, stats,
                (hipStream_t)stream);
 }
 
@@ -2556,16 +2661,17 @@ tvl1_status tvl1_calc_f32(tvl1_ctx *c, const float *I0, size_t pitch0, const flo
   HIP_TRY(c, hipSetDevice(c->device));
   s = ensure_geometry(c, W, H, (hipStream_t)stream);
   if (s != TVL1_OK) return s;
-  return solve(c, Frames{I0, I1, pitch0, pitch1, true}, W, H, u, v, fpitch, stats,
+  return solve(c, Frames{I0, I1, pitch0, pitch1, true}, nullptr, W, H, u, v, fpitch, stats,
                (hipStream_t)stream);
 }
 
 
-tvl1_status tvl1_calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
-                            size_t pair_stride0, const uint8_t *I1, size_t pitch1,
-                            size_t pair_stride1, int32_t W, int32_t H, float *u, float *v,
-                            size_t fpitch, size_t flow_pair_stride, tvl1_stats *stats,
-                            void *stream) {
+// tvl1_calc_batch (seed null) and tvl1_calc_batch_init (seed of pair 0, stride to the next)
+static tvl1_status calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                              size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                              size_t pair_stride1, const Seed *seed, int32_t W, int32_t H,
+                              float *u, float *v, size_t fpitch, size_t flow_pair_stride,
+                              tvl1_stats *stats, void *stream) {
   if (n <= 0) return set_err(c, TVL1_EINVAL, "batch size must be > 0 (got %d)", n);
   tvl1_status s = check_call(c, I0, pitch0, I1, pitch1, W, H, u, v, fpitch);
   if (s != TVL1_OK) return s;
@@ -2613,11 +2719,15 @@ tvl1_status tvl1_calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pi
     const uint8_t *i0 = I0 + (size_t)b0 * pair_stride0, *i1 = I1 + (size_t)b0 * pair_stride1;
     float *ub = reinterpret_cast<float *>(reinterpret_cast<char *>(u) + (size_t)b0 * flow_pair_stride);
     float *vb = reinterpret_cast<float *>(reinterpret_cast<char *>(v) + (size_t)b0 * flow_pair_stride);
-    s = batched ? solve_batch_chunk(c, m, i0, pitch0, pair_stride0, i1, pitch1, pair_stride1, W,
+    Seed sb{};
+    if (seed) sb = Seed{seed->u0 + (size_t)b0 * seed->stride, seed->v0 + (size_t)b0 * seed->stride,
+                        seed->pitch, seed->stride};
+    const Seed *sd = seed ? &sb : nullptr;
+    s = batched ? solve_batch_chunk(c, m, i0, pitch0, pair_stride0, i1, pitch1, pair_stride1, sd, W,
                                     H, ub, vb, fpitch, flow_pair_stride, stats ? stats + b0 : nullptr,
                                     (hipStream_t)stream)
-                : solve(c, Frames{i0, i1, pitch0, pitch1, false}, W, H, ub, vb, fpitch, stats ? stats + b0 : nullptr,
-                        (hipStream_t)stream);
+                : solve(c, Frames{i0, i1, pitch0, pitch1, false}, sd, W, H, ub, vb, fpitch,
+                        stats ? stats + b0 : nullptr, (hipStream_t)stream);
     if (s == TVL1_ENOMEM && batched && m > 1) {
       chunk = m / 2;
       continue;
@@ -2626,6 +2736,31 @@ tvl1_status tvl1_calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pi
     b0 += m;
   }
   return TVL1_OK;
+}
+
+tvl1_status tvl1_calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                            size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                            size_t pair_stride1, int32_t W, int32_t H, float *u, float *v,
+                            size_t fpitch, size_t flow_pair_stride, tvl1_stats *stats,
+                            void *stream) {
+  return calc_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, nullptr, W, H, u, v,
+                    fpitch, flow_pair_stride, stats, stream);
+}
+
+tvl1_status tvl1_calc_batch_init(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                                 size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                                 size_t pair_stride1, int32_t W, int32_t H, const float *u0,
+                                 const float *v0, size_t init_pitch, size_t init_pair_stride,
+                                 float *u, float *v, size_t fpitch, size_t flow_pair_stride,
+                                 tvl1_stats *stats, void *stream) {
+  tvl1_status s = check_seed(c, u0, v0, init_pitch, W);
+  if (s != TVL1_OK) return s;
+  if (init_pair_stride % sizeof(float) ||
+      (n > 1 && H > 0 && init_pair_stride != 0 && init_pair_stride < init_pitch * (size_t)H))
+    return set_err(c, TVL1_EINVAL, "initial flow pair stride must be 0 or cover one field, in whole floats");
+  const Seed seed{u0, v0, init_pitch / sizeof(float), init_pair_stride / sizeof(float)};
+  return calc_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, &seed, W, H, u, v,
+                    fpitch, flow_pair_stride, stats, stream);
 }
 
 
@@ -2870,9 +3005,12 @@ tvl1_status tvl1_postprocess_affine(tvl1_ctx *c, float *u, float *v, size_t fp, 
   return TVL1_OK;
 }
 
-tvl1_status tvl1_calc_host(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
-                           size_t pitch1, int32_t W, int32_t H, float *u, float *v,
-                           size_t fpitch, tvl1_stats *stats) {
+// tvl1_calc_host, and tvl1_calc_host_init with a host seed (u0, v0, row pitch ipitch bytes):
+// the seed is uploaded into the output staging planes, which the solve reads before its
+// last kernel writes them (the in/out flow of tvl1_calc_init)
+static tvl1_status calc_host(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
+                             size_t pitch1, int32_t W, int32_t H, const float *u0, const float *v0,
+                             size_t ipitch, float *u, float *v, size_t fpitch, tvl1_stats *stats) {
   tvl1_status s = check_call(c, I0, pitch0, I1, pitch1, W, H, u, v, fpitch);
   if (s != TVL1_OK) return s;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2883,8 +3021,15 @@ tvl1_status tvl1_calc_host(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const 
   // GpuMat::upload (optflow.cpp:315-316)
   HIP_TRY(c, hipMemcpy2DAsync(c->in0, P0, I0, pitch0, W, H, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpy2DAsync(c->in1, P0, I1, pitch1, W, H, hipMemcpyHostToDevice, st));
-  s = solve(c, Frames{c->in0, c->in1, P0, P0, false}, W, H, c->outu, c->outv, P0 * sizeof(float),
-            stats, st);
+  const Seed seed{c->outu, c->outv, P0, 0};
+  if (u0) {
+    HIP_TRY(c, hipMemcpy2DAsync(c->outu, P0 * sizeof(float), u0, ipitch, W * sizeof(float), H,
+                                hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpy2DAsync(c->outv, P0 * sizeof(float), v0, ipitch, W * sizeof(float), H,
+                                hipMemcpyHostToDevice, st));
+  }
+  s = solve(c, Frames{c->in0, c->in1, P0, P0, false}, u0 ? &seed : nullptr, W, H, c->outu, c->outv,
+            P0 * sizeof(float), stats, st);
   if (s != TVL1_OK) return s;
   // download (optflow.cpp:475-476)
   HIP_TRY(c, hipMemcpy2DAsync(u, fpitch, c->outu, P0 * sizeof(float), W * sizeof(float), H,
@@ -2893,6 +3038,21 @@ tvl1_status tvl1_calc_host(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const 
                               hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   return TVL1_OK;
+}
+
+tvl1_status tvl1_calc_host(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
+                           size_t pitch1, int32_t W, int32_t H, float *u, float *v,
+                           size_t fpitch, tvl1_stats *stats) {
+  return calc_host(c, I0, pitch0, I1, pitch1, W, H, nullptr, nullptr, 0, u, v, fpitch, stats);
+}
+
+tvl1_status tvl1_calc_host_init(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
+                                size_t pitch1, int32_t W, int32_t H, const float *u0,
+                                const float *v0, size_t init_pitch, float *u, float *v,
+                                size_t fpitch, tvl1_stats *stats) {
+  const tvl1_status s = check_seed(c, u0, v0, init_pitch, W);
+  if (s != TVL1_OK) return s;
+  return calc_host(c, I0, pitch0, I1, pitch1, W, H, u0, v0, init_pitch, u, v, fpitch, stats);
 }
 
 tvl1_status tvl1_postprocess_batch(tvl1_ctx *c, int32_t n, float *u, float *v, size_t fpitch,

@@ -248,6 +248,22 @@ __global__ void k_upsample(const float *__restrict__ s1, const float *__restrict
   dst[(size_t)y * dp + x] = c < 2 ? r * mul : r;
 }
 
+// [A.2b] One step of the initial-flow pyramid (useInitialFlow): cuda::resize of u1, u2 to the
+// next coarser level with the image pyramid's step, then cuda::multiply(scaleStep) as a
+// rounding of its own (like k_upsample's mul).  blockIdx.z = component.  The first step reads
+// the caller's seed planes, so the source pitch sp (floats) is not a level pitch.
+template <bool C>
+__global__ void k_flow_down(const float *__restrict__ s1, const float *__restrict__ s2, int sw,
+                            int sh, int sp, float *__restrict__ d1, float *__restrict__ d2,
+                            int dw, int dh, int dp, float fx, float fy, float mul) {
+  const int x = blockIdx.x * 64 + threadIdx.x;
+  const int y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= dw || y >= dh) return;
+  const float *src = blockIdx.z == 0 ? s1 : s2;
+  float *dst = blockIdx.z == 0 ? d1 : d2;
+  dst[(size_t)y * dp + x] = resize_px<C>(src, sw, sh, sp, x, y, fx, fy) * mul;
+}
+
 // ---------------------------------------------------------------- K3 gradient
 // centeredGradient of I1, written interleaved (I1, I1x, I1y, 0) for the K5 gather.
 TVL1_PLAIN __global__ void k_gradient(const float *__restrict__ I, int W, int H, int P,

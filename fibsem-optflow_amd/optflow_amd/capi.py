@@ -170,6 +170,24 @@ def load_engine() -> C.CDLL:
                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                     C.POINTER(TVL1Stats), C.c_void_p]
     lib.tvl1_calc_batch.restype = C.c_int
+    # solves from a caller-supplied flow (added under ABI 9)
+    lib.tvl1_calc_init.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TVL1Stats),
+                                   C.c_void_p]
+    lib.tvl1_calc_init.restype = C.c_int
+    lib.tvl1_calc_host_init.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t,
+                                        C.POINTER(C.c_uint8), C.c_size_t, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t,
+                                        C.POINTER(TVL1Stats)]
+    lib.tvl1_calc_host_init.restype = C.c_int
+    lib.tvl1_calc_batch_init.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t,
+                                         C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                         C.POINTER(TVL1Stats), C.c_void_p]
+    lib.tvl1_calc_batch_init.restype = C.c_int
     lib.tvl1_align_params_default.argtypes = [C.POINTER(TVL1AlignParams)]
     lib.tvl1_align_params_default.restype = None
     lib.tvl1_find_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
@@ -269,7 +287,10 @@ class Engine:
             msg = self.lib.tvl1_last_error(self.ctx)
             raise TVL1Error(f"{what}: {STATUS.get(rc, rc)}: {msg.decode() if msg else ''}")
 
-    def calc_host(self, I0: np.ndarray, I1: np.ndarray, warp_iters: bool = True):
+    def calc_host(self, I0: np.ndarray, I1: np.ndarray, warp_iters: bool = True, init=None):
+        """tvl1_calc_host; init = (u0, v0[, pitch]): tvl1_calc_host_init from that flow (float32
+        arrays of the frame's size with unit column stride; pitch in bytes, default their row
+        stride)."""
         I0 = np.ascontiguousarray(I0, dtype=np.uint8)
         I1 = np.ascontiguousarray(I1, dtype=np.uint8)
         h, w = I0.shape
@@ -284,9 +305,21 @@ class Engine:
             wi = np.full(cap, -1, np.int32)
             st.warp_iterations = wi.ctypes.data_as(C.POINTER(C.c_int32))
             st.warp_iterations_capacity = cap
-        rc = self.lib.tvl1_calc_host(self.ctx, _u8_ptr(I0), w, _u8_ptr(I1), w, w, h,
-                                     _f32_ptr(u), _f32_ptr(v), 4 * w, C.byref(st))
-        self._check(rc, "tvl1_calc_host")
+        if init is None:
+            rc = self.lib.tvl1_calc_host(self.ctx, _u8_ptr(I0), w, _u8_ptr(I1), w, w, h,
+                                         _f32_ptr(u), _f32_ptr(v), 4 * w, C.byref(st))
+            self._check(rc, "tvl1_calc_host")
+        else:
+            u0, v0 = (np.asarray(a, dtype=np.float32) for a in init[:2])
+            if u0.shape != (h, w) or v0.shape != (h, w):
+                raise ValueError("the initial flow must have the frames' size")
+            if u0.strides[1] != 4 or v0.strides[1] != 4 or u0.strides[0] != v0.strides[0]:
+                raise ValueError("the initial flow planes need unit column stride and one row pitch")
+            ipitch = int(init[2]) if len(init) > 2 else u0.strides[0]
+            rc = self.lib.tvl1_calc_host_init(self.ctx, _u8_ptr(I0), w, _u8_ptr(I1), w, w, h,
+                                              _f32_ptr(u0), _f32_ptr(v0), ipitch, _f32_ptr(u),
+                                              _f32_ptr(v), 4 * w, C.byref(st))
+            self._check(rc, "tvl1_calc_host_init")
         sd = stats_dict(st)
         if wi is not None:
             wi = wi[: sd["levels"] * self.params.warps].reshape(sd["levels"], self.params.warps)
@@ -294,9 +327,12 @@ class Engine:
 
     def calc_device(self, dI0: int, pitch0: int, dI1: int, pitch1: int, w: int, h: int,
                     du: int, dv: int, flow_pitch: int, stream: int = 0, stats: bool = True,
-                    warp_iters: bool = False, f32: bool = False):
+                    warp_iters: bool = False, f32: bool = False, init=None):
         """tvl1_calc on device buffers (u8 frames, pitches in bytes), or tvl1_calc_f32 with
-        f32=True (float frames in [0, 1], pitches in bytes)."""
+        f32=True (float frames in [0, 1], pitches in bytes).  init = (du0, dv0[, pitch]):
+        tvl1_calc_init from that flow (device pointers; pitch in bytes, default 4 * w)."""
+        if init is not None and f32:
+            raise ValueError("tvl1_calc_f32 takes no initial flow")
         st = TVL1Stats() if stats or warp_iters else None
         wi = None
         if warp_iters:
@@ -304,12 +340,21 @@ class Engine:
             wi = np.full(cap, -1, np.int32)
             st.warp_iterations = wi.ctypes.data_as(C.POINTER(C.c_int32))
             st.warp_iterations_capacity = cap
-        fn = self.lib.tvl1_calc_f32 if f32 else self.lib.tvl1_calc
-        rc = fn(self.ctx, C.c_void_p(dI0), pitch0, C.c_void_p(dI1), pitch1,
-                w, h, C.c_void_p(du), C.c_void_p(dv), flow_pitch,
-                C.byref(st) if st is not None else None,
-                C.c_void_p(stream) if stream else None)
-        self._check(rc, "tvl1_calc_f32" if f32 else "tvl1_calc")
+        if init is None:
+            fn = self.lib.tvl1_calc_f32 if f32 else self.lib.tvl1_calc
+            rc = fn(self.ctx, C.c_void_p(dI0), pitch0, C.c_void_p(dI1), pitch1,
+                    w, h, C.c_void_p(du), C.c_void_p(dv), flow_pitch,
+                    C.byref(st) if st is not None else None,
+                    C.c_void_p(stream) if stream else None)
+            self._check(rc, "tvl1_calc_f32" if f32 else "tvl1_calc")
+        else:
+            ipitch = int(init[2]) if len(init) > 2 else 4 * w
+            rc = self.lib.tvl1_calc_init(self.ctx, C.c_void_p(dI0), pitch0, C.c_void_p(dI1), pitch1,
+                                         w, h, C.c_void_p(init[0]), C.c_void_p(init[1]), ipitch,
+                                         C.c_void_p(du), C.c_void_p(dv), flow_pitch,
+                                         C.byref(st) if st is not None else None,
+                                         C.c_void_p(stream) if stream else None)
+            self._check(rc, "tvl1_calc_init")
         if st is None:
             return None
         sd = stats_dict(st)
@@ -321,9 +366,11 @@ class Engine:
     def calc_batch_device(self, n: int, dI0: int, pitch0: int, stride0: int, dI1: int,
                           pitch1: int, stride1: int, w: int, h: int, du: int, dv: int,
                           flow_pitch: int, flow_stride: int, stream: int = 0,
-                          warp_iters: bool = False):
+                          warp_iters: bool = False, init=None):
         """tvl1_calc_batch on device buffers: n pairs of one size, pair b at base + b*stride
-        (bytes).  Returns one stats dict per pair (+ per-warp iterations if asked)."""
+        (bytes).  Returns one stats dict per pair (+ per-warp iterations if asked).  init =
+        (du0, dv0[, pitch[, stride]]): tvl1_calc_batch_init from those flows (device pointers;
+        bytes, default 4 * w and pitch * h; stride 0 = one seed for every pair)."""
         sts = (TVL1Stats * n)()
         wis = []
         if warp_iters:
@@ -333,11 +380,22 @@ class Engine:
                 sts[b].warp_iterations = wi.ctypes.data_as(C.POINTER(C.c_int32))
                 sts[b].warp_iterations_capacity = cap
                 wis.append(wi)
-        rc = self.lib.tvl1_calc_batch(self.ctx, n, C.c_void_p(dI0), pitch0, stride0,
-                                      C.c_void_p(dI1), pitch1, stride1, w, h, C.c_void_p(du),
-                                      C.c_void_p(dv), flow_pitch, flow_stride, sts,
-                                      C.c_void_p(stream) if stream else None)
-        self._check(rc, "tvl1_calc_batch")
+        if init is None:
+            rc = self.lib.tvl1_calc_batch(self.ctx, n, C.c_void_p(dI0), pitch0, stride0,
+                                          C.c_void_p(dI1), pitch1, stride1, w, h, C.c_void_p(du),
+                                          C.c_void_p(dv), flow_pitch, flow_stride, sts,
+                                          C.c_void_p(stream) if stream else None)
+            self._check(rc, "tvl1_calc_batch")
+        else:
+            ipitch = int(init[2]) if len(init) > 2 else 4 * w
+            istride = int(init[3]) if len(init) > 3 else ipitch * h
+            rc = self.lib.tvl1_calc_batch_init(self.ctx, n, C.c_void_p(dI0), pitch0, stride0,
+                                               C.c_void_p(dI1), pitch1, stride1, w, h,
+                                               C.c_void_p(init[0]), C.c_void_p(init[1]), ipitch,
+                                               istride, C.c_void_p(du), C.c_void_p(dv), flow_pitch,
+                                               flow_stride, sts,
+                                               C.c_void_p(stream) if stream else None)
+            self._check(rc, "tvl1_calc_batch_init")
         out = [stats_dict(sts[b]) for b in range(n)]
         if warp_iters:
             for b in range(n):

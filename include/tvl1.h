@@ -71,7 +71,9 @@ typedef struct tvl1_params {
   int32_t iterations;  /* 300   optflow.cpp:509 */
   double scale_step;   /* 0.8   optflow.cpp:510 */
   double gamma;        /* 0.0   optflow.cpp:511 */
-  int32_t use_initial_flow; /* read at optflow.cpp:512 but NOT passed to create() (:518): ignored, as in the reference */
+  int32_t use_initial_flow; /* read at optflow.cpp:512 but NOT passed to create() (:518): ignored by every
+                               entry point, as in the reference; a solve that starts from a flow is a call
+                               of its own, tvl1_calc_init */
   int32_t median_filtering; /* build-only: 1 = off (reference behaviour); 3 or 5 = median of u,v before each warp */
   int32_t fast_math;   /* build-only arithmetic mode:
                           0 = IEEE float32, no contraction: bit-identical to oracle/ (default);
@@ -168,6 +170,46 @@ tvl1_status tvl1_calc_batch(tvl1_ctx *ctx, int32_t n,
                             int32_t width, int32_t height,
                             float *u, float *v, size_t flow_pitch, size_t flow_pair_stride,
                             tvl1_stats *stats, void *stream);
+
+/* ---- Solves that start from a caller-supplied flow (added under ABI 9) ----
+ * cv::cuda::OpticalFlowDual_TVL1::calc with useInitialFlow = true: level 0 of the flow
+ * pyramid is the seed (u0, v0), each coarser level is cuda::resize(INTER_LINEAR) of the one
+ * before times scaleStep, and the coarsest level of that chain replaces the zero flow the
+ * solve otherwise starts from (u3 stays zero there for gamma != 0).  Everything else is
+ * tvl1_calc.  u0, v0: device f32 planes of the frame's size, row pitch init_pitch bytes
+ * (>= 4 * width, a multiple of 4).  u0 == u and v0 == v are allowed (OpenCV's in/out flow):
+ * the seed is read before the flow is written, on the same stream.  A null seed or a bad
+ * pitch is TVL1_EINVAL before anything is launched; so is a ctx with profile = 1. */
+tvl1_status tvl1_calc_init(tvl1_ctx *ctx,
+                           const uint8_t *I0, size_t pitch0,
+                           const uint8_t *I1, size_t pitch1,
+                           int32_t width, int32_t height,
+                           const float *u0, const float *v0, size_t init_pitch,
+                           float *u, float *v, size_t flow_pitch,
+                           tvl1_stats *stats, void *stream);
+
+/* tvl1_calc_init on HOST memory (frames, seed and flow; as tvl1_calc_host). */
+tvl1_status tvl1_calc_host_init(tvl1_ctx *ctx,
+                                const uint8_t *I0, size_t pitch0,
+                                const uint8_t *I1, size_t pitch1,
+                                int32_t width, int32_t height,
+                                const float *u0, const float *v0, size_t init_pitch,
+                                float *u, float *v, size_t flow_pitch,
+                                tvl1_stats *stats);
+
+/* tvl1_calc_batch from per-pair seeds: pair b's seed at u0 / v0 + b*init_pair_stride bytes
+ * (a multiple of 4; 0 = one seed for every pair).  Each pair's flow and per-warp iteration
+ * counts are those of tvl1_calc_init.  gamma != 0 solves the pairs one by one through
+ * tvl1_calc_init's path; in/out flow (u0 == u) then needs init_pair_stride ==
+ * flow_pair_stride and init_pitch == flow_pitch. */
+tvl1_status tvl1_calc_batch_init(tvl1_ctx *ctx, int32_t n,
+                                 const uint8_t *I0, size_t pitch0, size_t pair_stride0,
+                                 const uint8_t *I1, size_t pitch1, size_t pair_stride1,
+                                 int32_t width, int32_t height,
+                                 const float *u0, const float *v0, size_t init_pitch,
+                                 size_t init_pair_stride,
+                                 float *u, float *v, size_t flow_pitch, size_t flow_pair_stride,
+                                 tvl1_stats *stats, void *stream);
 
 /* ---- Feature pre-alignment (features.cpp:46-167, optflow.cpp:366-377) ----
  * find_alignment(frame1, frame0): ORB keypoints and descriptors on the GPU, brute-force
