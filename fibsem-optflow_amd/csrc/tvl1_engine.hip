@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/tvl1.h"
+#include "tvl1_plan.hpp"
 #include "tvl1_kernels.hpp"
 #include "tvl1_batch.hpp"
 #include "tvl1_align.hpp"
@@ -38,9 +39,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-constexpr int kStripRows = 32;   // rows per wave strip in k_iterate
-constexpr int kTbMax = 4;        // max iterations fused per pass in k_iterate_tb
-constexpr int kRollMinSeg = 8;   // smallest k_iterate_roll segment (rows)
 #ifndef TVL1_WI_M
 #define TVL1_WI_M 6
 #endif
@@ -56,9 +54,6 @@ constexpr int kWiMargin = TVL1_WI_M;
 constexpr int kBatchPx1W = 1700;
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-// IterArgs::taut_small: the projection's ng = 1 + taut*g ignores g below 2^-48 when |taut|
-// <= 2^20, so sqrt_nn may skip its (0, 2^-96) form (tvl1_kernels.hpp, sqrt_nn); NaN: false
-inline int taut_small(float taut) { return std::fabs(taut) <= 0x1p20f ? 1 : 0; }
 
 struct Geometry {
   int W = 0, H = 0, L = 0;
@@ -264,21 +259,6 @@ static tvl1_status check_params(tvl1_ctx *c, const tvl1_params *p) {
   return TVL1_OK;
 }
 
-// Pyramid sizes exactly as calcImpl: round-half-even(cols*step), stop < 16.
-static int pyramid_sizes(int w, int h, int nscales, double step, int *ws, int *hs) {
-  int L = nscales < TVL1_MAX_LEVELS ? nscales : TVL1_MAX_LEVELS;
-  ws[0] = w;
-  hs[0] = h;
-  for (int s = 1; s < L; ++s) {
-    const int nw = (int)std::lrint((double)ws[s - 1] * step);
-    const int nh = (int)std::lrint((double)hs[s - 1] * step);
-    if (nw < 16 || nh < 16) return s;
-    ws[s] = nw;
-    hs[s] = nh;
-  }
-  return L;
-}
-
 // Arithmetic mode of a solve (kIEEE / kFast / kFma, tvl1_kernels.hpp): tvl1_params.fast_math
 // for the gamma = 0 path with 0 <= tau/theta < inf; gamma != 0 and taut < 0 solves run the
 // IEEE kernels.
@@ -286,35 +266,6 @@ static int math_of(const tvl1_params &p) {
   const float taut = (float)(p.tau / p.theta);
   const bool exact_div = !(taut >= 0.0f && taut <= FLT_MAX);
   return p.gamma != 0.0 || exact_div ? kIEEE : p.fast_math;
-}
-
-// Rows per k_iterate_roll segment.  Every wavefront runs (rows + 2K) steps, so the pass
-// takes about rounds x (rows + 2K) step times, rounds = ceil(wavefronts / resident slots):
-// pick the split into segments that minimises that (a partial last round idles most of
-// the device; short segments repeat the 2K-row halo).
-static int roll_segment(int bands, int lh, int k, int slots) {
-  if (slots <= 0) slots = 4096;
-  int best = lh;
-  long best_cost = -1;
-  for (int R = 1; R <= 4; ++R) {
-    const int segs = std::max(1, R * slots / bands);
-    const int seg = std::max(kRollMinSeg, (lh + segs - 1) / segs);
-    const long waves = (long)bands * ((lh + seg - 1) / seg);
-    const long rounds = (waves + slots - 1) / slots;
-    const long cost = rounds * (seg + 2 * k);
-    if (best_cost < 0 || cost < best_cost) {
-      best_cost = cost;
-      best = seg;
-    }
-  }
-  return best;
-}
-
-static int iterate_blocks(int W, int H) {
-  const int segs = (W + kSegPx - 1) / kSegPx;
-  const int strips = (H + kStripRows - 1) / kStripRows;
-  const int waves = segs * strips;
-  return (waves + 3) / 4;
 }
 
 // (Re)allocate one of the ctx's scratch arenas, zero-filled, for work on stream `use`.
@@ -463,11 +414,7 @@ static tvl1_status ensure_geometry(tvl1_ctx *c, int W, int H, hipStream_t st) {
   bytes += 2 * 3 * plane;                   // C[2]
   bytes += 2 * align_up(P0 * H, 256);       // in0, in1 (u8)
   bytes += 2 * plane;                       // outu, outv
-  // residual partials: k_iterate_tb worst case (RH 32 at 4 iterations: 56 x 24 px per
-  // block), k_iterate_roll worst case (56-px bands, segments of kRollMinSeg rows)
-  const int tb_blocks = ((W + 55) / 56) * ((H + 23) / 24);
-  const int roll_waves = ((W + 55) / 56) * ((H + kRollMinSeg - 1) / kRollMinSeg);
-  const int nblk = std::max(std::max(iterate_blocks(W, H), tb_blocks), roll_waves) + 64;
+  const int nblk = partials_capacity(W, H);   // residual partials
   bytes += align_up((size_t)nblk * sizeof(double), 256);
   bytes += 4096;                            // alignment slack
 
@@ -535,18 +482,112 @@ static inline dim3 grid2(int w, int h, int z = 1) {
 }
 static const dim3 kBlk2(64, 4, 1);
 
-// SURVEY 8(d) byte model with executed iteration counts (reported in stats).
-static double survey_bytes(const Geometry &g, int warps, const int64_t *iters) {
-  double B = 0.0;
-  for (int l = 0; l < g.L; ++l) {
-    const double N = (double)g.ws[l] * g.hs[l];
-    B += N * (12.0 + 16.0 + 40.0 * warps + 64.0 * (double)iters[l]);
-    if (l >= 1) B += N * 8.0;
-    if (l < g.L - 1) B += N * 8.0;
+#define TVL1_TRY(expr)                 \
+  do {                                 \
+    tvl1_status r_ = (expr);           \
+    if (r_ != TVL1_OK) return r_;      \
+  } while (0)
+
+// ---- fills shared by the solve paths
+// IterArgs scalars of a level: its sizes, the solver's float parameters and where the residual
+// partials go (plane pointers and flags are set per pass)
+static IterArgs iter_args(const tvl1_params &prm, int lw, int lh, int P, double *partials) {
+  IterArgs a{};
+  a.W = lw;
+  a.H = lh;
+  a.P = P;
+  a.segs = (lw + kSegPx - 1) / kSegPx;
+  a.strip_rows = kStripRows;
+  a.l_t = (float)(prm.lambda * prm.theta);
+  a.theta = (float)prm.theta;
+  a.gamma = (float)prm.gamma;
+  a.taut = (float)(prm.tau / prm.theta);
+  a.taut_small = taut_small(a.taut);
+  a.partials = partials;
+  return a;
+}
+
+// source and destination planes of the buffer sets (ui, pi), warp constants of set cb
+static void set_planes(const tvl1_ctx *c, IterArgs &a, int ui, int pi, int cb) {
+  a.u1s = c->U[ui][0]; a.u2s = c->U[ui][1]; a.u3s = c->U[ui][2];
+  a.u1d = c->U[ui ^ 1][0]; a.u2d = c->U[ui ^ 1][1]; a.u3d = c->U[ui ^ 1][2];
+  a.p11s = c->Pd[pi][0]; a.p12s = c->Pd[pi][1]; a.p21s = c->Pd[pi][2];
+  a.p22s = c->Pd[pi][3]; a.p31s = c->Pd[pi][4]; a.p32s = c->Pd[pi][5];
+  a.p11d = c->Pd[pi ^ 1][0]; a.p12d = c->Pd[pi ^ 1][1]; a.p21d = c->Pd[pi ^ 1][2];
+  a.p22d = c->Pd[pi ^ 1][3]; a.p31d = c->Pd[pi ^ 1][4]; a.p32d = c->Pd[pi ^ 1][5];
+  a.I1wx = c->C[cb][0];
+  a.I1wy = c->C[cb][1];
+  a.rho = c->C[cb][2];
+}
+
+// the u / p / constants plane tables of the batch arena (every batched argument block has them)
+template <class T>
+static void set_batch_u(const tvl1_ctx *c, T &t) {
+  for (int k = 0; k < 2; ++k)
+    for (int j = 0; j < 2; ++j) t.U[k][j] = c->bU[k][j];
+}
+template <class T>
+static void set_batch_uc(const tvl1_ctx *c, T &t) {
+  set_batch_u(c, t);
+  for (int j = 0; j < 3; ++j) t.C[j] = c->bC[j];
+}
+template <class T>
+static void set_batch_upc(const tvl1_ctx *c, T &t) {
+  set_batch_uc(c, t);
+  for (int k = 0; k < 2; ++k)
+    for (int j = 0; j < 4; ++j) t.Pp[k][j] = c->bP[k][j];
+}
+
+// Stats epilogue of a solve: levels, iteration counts, checks and misses (SURVEY 8(d) bytes
+// with the executed iterations); the per-kernel-class figures start at zero (put_class_totals)
+static void fill_stats(tvl1_stats *s, const Geometry &g, int warps, const int64_t *level_iters,
+                       int64_t checks, int32_t misses) {
+  s->levels = g.L;
+  int64_t tot = 0;
+  for (int l = 0; l < TVL1_MAX_LEVELS; ++l) {
+    s->level_width[l] = l < g.L ? g.ws[l] : 0;
+    s->level_height[l] = l < g.L ? g.hs[l] : 0;
+    s->level_iterations[l] = l < g.L ? level_iters[l] : 0;
+    tot += l < g.L ? level_iters[l] : 0;
   }
-  const double N0 = (double)g.ws[0] * g.hs[0];
-  B += N0 * (2.0 + 8.0) + N0 * 8.0;
-  return B;
+  s->iterations_total = tot;
+  s->checks_total = checks;
+  s->speculation_misses = misses;
+  s->algorithmic_bytes = survey_bytes(g.L, g.ws, g.hs, warps, level_iters);
+  for (int k = 0; k < 4; ++k) {
+    s->kernel_ms[k] = 0.0;
+    s->kernel_launches[k] = 0;
+    s->kernel_bytes[k] = 0.0;
+    s->kernel_hbm_bytes[k] = 0.0;
+  }
+}
+
+// Per-kernel-class totals of the profiling marks of a solve (tvl1_set_profiling): waits for
+// the last mark's event
+struct ClassTotals {
+  double ms[4] = {}, bytes[4] = {}, hbm[4] = {};
+  int64_t launches[4] = {};
+};
+static tvl1_status sum_marks(tvl1_ctx *c, ClassTotals &t) {
+  if (!c->profiling || c->marks.empty()) return TVL1_OK;
+  HIP_TRY(c, hipEventSynchronize(c->ev_pool[c->marks.back().b]));
+  for (const auto &m : c->marks) {
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_pool[m.a], c->ev_pool[m.b]));
+    t.ms[m.cls] += ms;
+    t.launches[m.cls] += 1;
+    t.bytes[m.cls] += m.bytes;
+    t.hbm[m.cls] += m.hbm_bytes;
+  }
+  return TVL1_OK;
+}
+static void put_class_totals(tvl1_stats *s, const ClassTotals &t) {
+  for (int k = 0; k < 4; ++k) {
+    s->kernel_ms[k] = t.ms[k];
+    s->kernel_launches[k] = t.launches[k];
+    s->kernel_bytes[k] = t.bytes[k];
+    s->kernel_hbm_bytes[k] = t.hbm[k];
+  }
 }
 
 // calcImpl + procOneScale on device inputs already in the arena
@@ -616,12 +657,6 @@ static tvl1_status read_residual(tvl1_ctx *c, hipStream_t st, int nparts, double
   return wait_check(c, st, seq, out);
 }
 
-// resize(): an exact 2x downscale of INTER_LINEAR takes the INTER_AREA fast path
-static int area_fast_of(double sx, double sy) {
-  const int ix = (int)std::lrint(sx), iy = (int)std::lrint(sy);
-  return std::fabs(sx - ix) < DBL_EPSILON && std::fabs(sy - iy) < DBL_EPSILON && ix == 2 && iy == 2;
-}
-
 // Profile 1 (tvl1_params.profile): the schedule of OpenCV's CPU
 // cv::DualTVL1OpticalFlow::calc / procOneScale, restated in oracle/tvl1_oracle_dualtvl1.c.
 // Per warp: remap (k_remap_cubic), then up to outerIterations rounds, each starting with
@@ -676,7 +711,6 @@ static tvl1_status solve_dualtvl1(tvl1_ctx *c, const Frames &in, int W, int H, f
     const size_t n = (size_t)g.ps[L - 1] * g.hs[L - 1] * sizeof(float);
     for (int k = 0; k < (gam ? 3 : 2); ++k) HIP_TRY(c, hipMemsetAsync(c->U[ui][k], 0, n, st));
   }
-  const float l_t = (float)(prm.lambda * prm.theta);
   const float taut = (float)(prm.tau / prm.theta);
   const bool exact_div = !(taut >= 0.0f && taut <= FLT_MAX);
   const float upmul = (float)(1.0 / prm.scale_step);
@@ -685,22 +719,8 @@ static tvl1_status solve_dualtvl1(tvl1_ctx *c, const Frames &in, int W, int H, f
     const int lw = g.ws[s], lh = g.hs[s], P = g.ps[s];
     const float scaledEps = (float)(prm.epsilon * prm.epsilon * (double)(lw * lh));
     hipLaunchKernelGGL(k_gradient, grid2(lw, lh), kBlk2, 0, st, c->I1s[s], lw, lh, P, c->G);
-    IterArgs a{};
-    a.W = lw;
-    a.H = lh;
-    a.P = P;
-    a.segs = (lw + kSegPx - 1) / kSegPx;
-    a.strip_rows = kStripRows;
-    a.l_t = l_t;
-    a.theta = (float)prm.theta;
-    a.gamma = (float)prm.gamma;
-    a.taut = taut;
-    a.taut_small = taut_small(taut);
-    a.partials = c->partials;
+    IterArgs a = iter_args(prm, lw, lh, P, c->partials);
     a.calc_err = 1;
-    a.I1wx = c->C[0][0];
-    a.I1wy = c->C[0][1];
-    a.rho = c->C[0][2];
     const int nblk = iterate_blocks(lw, lh);
     bool p_zero = true;
     for (int wp = 0; wp < prm.warps; ++wp) {
@@ -719,12 +739,7 @@ static tvl1_status solve_dualtvl1(tvl1_ctx *c, const Frames &in, int W, int H, f
           ui ^= 1;
         }
         for (int ni = 0; error > scaledEps && ni < prm.inner_iterations; ++ni) {
-          a.u1s = c->U[ui][0]; a.u2s = c->U[ui][1]; a.u3s = c->U[ui][2];
-          a.u1d = c->U[ui ^ 1][0]; a.u2d = c->U[ui ^ 1][1]; a.u3d = c->U[ui ^ 1][2];
-          a.p11s = c->Pd[pi][0]; a.p12s = c->Pd[pi][1]; a.p21s = c->Pd[pi][2];
-          a.p22s = c->Pd[pi][3]; a.p31s = c->Pd[pi][4]; a.p32s = c->Pd[pi][5];
-          a.p11d = c->Pd[pi ^ 1][0]; a.p12d = c->Pd[pi ^ 1][1]; a.p21d = c->Pd[pi ^ 1][2];
-          a.p22d = c->Pd[pi ^ 1][3]; a.p31d = c->Pd[pi ^ 1][4]; a.p32d = c->Pd[pi ^ 1][5];
+          set_planes(c, a, ui, pi, 0);
           a.p_zero = p_zero ? 1 : 0;
           if (gam && exact_div)
             hipLaunchKernelGGL((k_iterate<true, true, true>), dim3(nblk), dim3(kBlock), 0, st, a);
@@ -765,24 +780,8 @@ static tvl1_status solve_dualtvl1(tvl1_ctx *c, const Frames &in, int W, int H, f
                      g.ps[0], u, v, fpitch);
   HIP_TRY(c, hipGetLastError());
   if (stats) {
-    stats->levels = L;
-    int64_t tot = 0;
-    for (int s = 0; s < TVL1_MAX_LEVELS; ++s) {
-      stats->level_width[s] = s < L ? g.ws[s] : 0;
-      stats->level_height[s] = s < L ? g.hs[s] : 0;
-      stats->level_iterations[s] = s < L ? level_iters[s] : 0;
-      tot += s < L ? level_iters[s] : 0;
-    }
-    stats->iterations_total = tot;
-    stats->checks_total = tot;
-    stats->speculation_misses = 0;
-    stats->algorithmic_bytes = survey_bytes(g, prm.warps, level_iters);
-    for (int k = 0; k < 4; ++k) {
-      stats->kernel_ms[k] = 0.0;
-      stats->kernel_launches[k] = 0;
-      stats->kernel_bytes[k] = 0.0;
-      stats->kernel_hbm_bytes[k] = 0.0;
-    }
+    fill_stats(stats, g, prm.warps, level_iters, 0, 0);
+    stats->checks_total = stats->iterations_total;   // every iteration evaluates the residual
   }
   return TVL1_OK;
 }
@@ -796,6 +795,425 @@ struct SolveCount {
   explicit SolveCount(int dev) : d(dev & 63) { g_solving[d].fetch_add(1, std::memory_order_relaxed); }
   ~SolveCount() { g_solving[d].fetch_sub(1, std::memory_order_relaxed); }
 };
+
+// share of the resident slots a streaming launch is sized for: all of them for a solve
+// alone on its device, fill_shared while other solves are in progress (their blocks fill
+// the rest instead of waiting for this launch's last round).  Segmentation never changes
+// a result (tests/test_gpu_parity.py TVL1_ROLL_SEG cases)
+static int fill_now(const tvl1_ctx *c) {
+  return g_solving[c->device & 63].load(std::memory_order_relaxed) > 1 ? c->fill_shared : c->fill;
+}
+
+// ---------------------------------------------------------------- single-pair launchers
+// The streaming kernels (k_iterate_roll, k_warp_ring, k_warp_iter) take 32-bit buffer
+// byte offsets, and the iteration passes address a whole plane group (RollBufs: up to 6
+// planes at the level-0 plane stride) through one descriptor: a level whose largest group
+// reaches c->buf_limit bytes uses the 64-bit-addressed kernels (k_warp_img, k_iterate_tb).
+static size_t plane_stride(const tvl1_ctx *c) {   // arena plane stride
+  return (size_t)c->geo.ps[0] * c->geo.H * sizeof(float);
+}
+static size_t group_bytes(const tvl1_ctx *c, int s, int planes) {
+  return (size_t)(planes - 1) * plane_stride(c) + (size_t)c->geo.ps[s] * c->geo.hs[s] * sizeof(float);
+}
+static bool buffer_ok(const tvl1_ctx *c, int s) {
+  return group_bytes(c, s, c->geo.gamma ? 6 : 4) < c->buf_limit;
+}
+// the planes of a pass as RollBufs groups (the arena keeps each set's planes contiguous)
+static RollBufs roll_bufs(const tvl1_ctx *c, int s, int uset, int pset, int cbuf) {
+  const bool gam = c->geo.gamma;
+  RollBufs b;
+  b.c = c->C[cbuf][0];
+  b.us = c->U[uset][0];
+  b.ud = c->U[uset ^ 1][0];
+  b.ps = c->Pd[pset][0];
+  b.pd = c->Pd[pset ^ 1][0];
+  b.pstride = (unsigned)plane_stride(c);
+  b.cb = (unsigned)group_bytes(c, s, 3);
+  b.ub = (unsigned)group_bytes(c, s, gam ? 3 : 2);
+  b.pb = (unsigned)group_bytes(c, s, gam ? 6 : 4);
+  return b;
+}
+
+// What the launchers need of one pyramid level of a single-pair solve
+struct Level {
+  tvl1_ctx *c;
+  hipStream_t st;
+  int s, lw, lh, P;
+  IterArgs a;        // the level's scalars (iter_args); planes and flags are set per pass
+  int math;          // kIEEE / kFast / kFma (math_of)
+  bool gam, exact_div;
+  bool roll_ok;      // the level's planes fit 32-bit buffer offsets (the streaming kernels)
+  bool roll_long;    // ... and passes of >= 3 iterations stream too
+};
+
+// K5 warpBackward of warp wp: the constants of set cbuf from the flow of set uset
+static tvl1_status gather(const Level &lv, int uset, int cbuf, int wp) {
+  tvl1_ctx *c = lv.c;
+  hipStream_t st = lv.st;
+  const int s = lv.s, lw = lv.lw, lh = lv.lh, P = lv.P;
+  size_t t0 = prof_begin(c, st);
+  if (!lv.roll_ok) {
+    const int tx = (lw + kWarpTW - 1) / kWarpTW, ty = (lh + kWarpTH - 1) / kWarpTH;
+#define WARP_IMG(FM)                                                                           \
+  hipLaunchKernelGGL(k_warp_img<FM>, dim3(tx * ty), dim3(256), 0, st, c->I0s[s], c->I1s[s],    \
+                     c->U[uset][0], c->U[uset][1], lw, lh, P, tx, c->C[cbuf][0], c->C[cbuf][1], \
+                     c->C[cbuf][2]);
+    MATH_SWITCH(lv.math, WARP_IMG)
+#undef WARP_IMG
+  } else {
+    WarpRingArgs wa;
+    wa.I0 = c->I0s[s];
+    wa.I1 = c->I1s[s];
+    wa.u1 = c->U[uset][0];
+    wa.u2 = c->U[uset][1];
+    wa.I1wx = c->C[cbuf][0];
+    wa.I1wy = c->C[cbuf][1];
+    wa.rho = c->C[cbuf][2];
+    wa.W = lw;
+    wa.H = lh;
+    wa.P = P;
+    const StreamPlan sp = plan_warp_ring(lw, lh, 6, fill_slots(c->warp_ring_slots, fill_now(c)), c->roll_seg);
+    wa.bands = sp.bands;
+    wa.seg_rows = sp.seg_rows;
+    wa.waves = sp.waves;
+#define WARP_RING(FM) \
+  hipLaunchKernelGGL((k_warp_ring<6, 2, FM>), dim3(wa.waves), dim3(128), 0, st, wa);
+    MATH_SWITCH(lv.math, WARP_RING)
+#undef WARP_RING
+  }
+  // algorithmic: 40 B/px per warp; compulsory here ~28 B/px (I1 x 1 + 2M/64)
+  prof_end(c, st, t0, 1, (double)lw * lh * 40.0, (double)lw * lh * 28.0);
+  DIAG(c, st, "warp kernel", s, wp, -1);
+  return TVL1_OK;
+}
+
+// the flow of level s (set uset) zoomed to level s-1 (set uset^1), scaled by 1/scaleStep
+static tvl1_status upsample(const Level &lv, int uset) {
+  tvl1_ctx *c = lv.c;
+  hipStream_t st = lv.st;
+  const Geometry &g = c->geo;
+  const int s = lv.s, lw = lv.lw, lh = lv.lh;
+  const int dw = g.ws[s - 1], dh = g.hs[s - 1];
+  const float fxu = (float)(1.0 / ((double)dw / lw));
+  const float fyu = (float)(1.0 / ((double)dh / lh));
+  const float upmul = (float)(1.0 / c->prm.scale_step);
+  size_t t0 = prof_begin(c, st);
+  if (contracts(lv.math))
+    hipLaunchKernelGGL(k_upsample<true>, grid2(dw, dh, lv.gam ? 3 : 2), kBlk2, 0, st, c->U[uset][0],
+                       c->U[uset][1], c->U[uset][2], lw, lh, g.ps[s], c->U[uset ^ 1][0],
+                       c->U[uset ^ 1][1], c->U[uset ^ 1][2], dw, dh, g.ps[s - 1], fxu, fyu, upmul);
+  else
+    hipLaunchKernelGGL(k_upsample<false>, grid2(dw, dh, lv.gam ? 3 : 2), kBlk2, 0, st, c->U[uset][0],
+                       c->U[uset][1], c->U[uset][2], lw, lh, g.ps[s], c->U[uset ^ 1][0],
+                       c->U[uset ^ 1][1], c->U[uset ^ 1][2], dw, dh, g.ps[s - 1], fxu, fyu, upmul);
+  prof_end(c, st, t0, 2, (double)lw * lh * 8.0 + (double)dw * dh * 8.0);
+  DIAG(c, st, "k_upsample", s, -1, -1);
+  return TVL1_OK;
+}
+
+// One iteration pass: k iterations (ending in a check if calc_end) from the buffer sets
+// (ui, pi) into (ui ^ 1, pi ^ 1), with the constants of set cb.  gate: a speculative launch
+// (DESIGN 4.8), which runs only if *gate == gseq.
+struct Pass {
+  int k;
+  bool calc_end;
+  int ui, pi, cb;
+  bool p_zero;
+  const unsigned long long *gate;
+  unsigned long long gseq;
+};
+
+// Each launcher takes the pass's IterArgs (planes and flags set), launches its kernel family
+// and returns the number of residual partials the pass wrote (-1: the ctx's error is set, a
+// TVL1_EHIP), with the compulsory HBM bytes of the launch in *hbm.
+static int partials_fit(tvl1_ctx *c, int need, int blocks, const char *what) {
+  if (need <= c->partials_cap) return blocks;
+  (void)set_err(c, TVL1_EHIP, "internal: %d %s > partials capacity %d", blocks, what, c->partials_cap);
+  return -1;
+}
+
+// the warp's first pass with warpBackward fused in (k_warp_iter), storing the constants if store_c
+static int launch_warp_iter(const Level &lv, const IterArgs &a, const Pass &p, bool store_c, double *hbm) {
+  tvl1_ctx *c = lv.c;
+  WarpIterArgs w;
+  w.ra.b = roll_bufs(c, lv.s, p.ui, p.pi, p.cb);
+  w.ra.it = a;
+  w.I0 = c->I0s[lv.s];
+  w.I1 = c->I1s[lv.s];
+  w.store_c = store_c ? 1 : 0;
+  constexpr int M = kWiMargin, BW = 128;
+  const StreamPlan sp = plan_warp_iter(lv.lw, lv.lh, BW, M, fill_slots(c->witer_slots, fill_now(c)), c->roll_seg);
+  w.ra.bands = sp.bands;
+  w.ra.seg_rows = sp.seg_rows;
+  w.ra.waves = sp.waves;
+  if (partials_fit(c, sp.waves, sp.waves, "blocks") < 0) return -1;
+#define WITER(FM)                                                                           \
+  if (c->wi_nc == 2)                                                                       \
+    hipLaunchKernelGGL((k_warp_iter<M, FM, BW, 1, 2>), dim3(w.ra.waves), dim3(128 + BW),    \
+                       c->probe_wi_lds, lv.st, w);                                          \
+  else                                                                                     \
+    hipLaunchKernelGGL((k_warp_iter<M, FM, BW, 1, 1>), dim3(w.ra.waves), dim3(64 + BW), 0, lv.st, w);
+  MATH_SWITCH(lv.math, WITER)
+#undef WITER
+  *hbm = warp_iter_hbm(sp, lv.lh, BW, wi_ww<M, BW>(), (double)lv.lw * lv.lh, p.p_zero, store_c);
+  return sp.waves;
+}
+
+// taut < 0 or not finite: one iteration per launch, IEEE divisions (k_iterate)
+static int launch_iterate(const Level &lv, const IterArgs &a, const Pass &p, double *hbm) {
+  const int nblk = iterate_blocks(lv.lw, lv.lh);
+  if (lv.gam)
+    hipLaunchKernelGGL((k_iterate<true, true>), dim3(nblk), dim3(kBlock), 0, lv.st, a);
+  else
+    hipLaunchKernelGGL((k_iterate<false, true>), dim3(nblk), dim3(kBlock), 0, lv.st, a);
+  *hbm = iterate_hbm((double)lv.lw * lv.lh, p.k, pass_planes(lv.gam, p.p_zero));
+  return nblk;
+}
+
+// the streaming pass (k_iterate_roll<G, K, PX>); midp: a 4-iteration pass that also keeps the
+// residual after 2 (k_iterate_roll_mid: two partials per wavefront)
+static int launch_roll(const Level &lv, const IterArgs &a, const Pass &p, bool midp, double *hbm) {
+  tvl1_ctx *c = lv.c;
+  hipStream_t st = lv.st;
+  const int k = p.k, math = lv.math;
+  const bool gam = lv.gam;
+  RollArgs ra;
+  ra.b = roll_bufs(c, lv.s, p.ui, p.pi, p.cb);
+  ra.it = a;
+  const int px = k <= 2 && (long)lv.lw * lv.lh >= c->roll_px4_min ? 4 : 2;
+  const int slots = midp ? c->mid_slots : c->roll_slots[k][gam][px];
+  const StreamPlan sp = plan_roll(lv.lw, lv.lh, k, px, fill_slots(slots, fill_now(c)), c->roll_seg);
+  ra.bands = sp.bands;
+  ra.seg_rows = sp.seg_rows;
+  ra.waves = sp.waves;   // one residual partial per wavefront (two for the mid pass)
+  if (partials_fit(c, (midp ? 2 : 1) * sp.waves, sp.waves, "wavefronts") < 0) return -1;
+  if (midp && (k != 4 || px != 2 || gam || !p.calc_end)) {
+    (void)set_err(c, TVL1_EHIP, "internal: mid-check pass of k = %d, px = %d", k, px);
+    return -1;
+  }
+  const dim3 grid((ra.waves + 3) / 4);
+#define ROLL_G(K, PX) \
+  hipLaunchKernelGGL((k_iterate_roll<true, K, PX>), grid, dim3(256), 0, st, ra);
+#define ROLL_M(FM, K, PX)                                                                  \
+  if (c->probe_lds > 0)                                                                    \
+    (void)hipFuncSetAttribute((const void *)k_iterate_roll<false, K, PX, FM>,              \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, c->probe_lds);   \
+  hipLaunchKernelGGL((k_iterate_roll<false, K, PX, FM>), grid, dim3(256), c->probe_lds, st, ra);
+#define ROLL(K, PX)                     \
+  if (gam) {                            \
+    ROLL_G(K, PX)                       \
+  } else if (math == kFast) {           \
+    ROLL_M(kFast, K, PX)                \
+  } else if (math == kFma) {            \
+    ROLL_M(kFma, K, PX)                 \
+  } else {                              \
+    ROLL_M(kIEEE, K, PX)                \
+  }
+#define MID_M(FM) hipLaunchKernelGGL((k_iterate_roll_mid<FM>), grid, dim3(256), 0, st, ra);
+  if (midp) {
+    MATH_SWITCH(math, MID_M)
+  } else if (px == 4) {   // k <= 2
+    if (k == 1) {
+      ROLL(1, 4)
+    } else {
+      ROLL(2, 4)
+    }
+  } else {
+    switch (k) {
+      case 1: ROLL(1, 2) break;
+      case 2: ROLL(2, 2) break;
+      case 3: ROLL(3, 2) break;
+      default: ROLL(4, 2) break;
+    }
+  }
+#undef MID_M
+#undef ROLL
+#undef ROLL_M
+#undef ROLL_G
+  *hbm = roll_hbm(sp, lv.lh, k, px, (double)lv.lw * lv.lh, pass_planes(gam, p.p_zero));
+  return sp.waves;
+}
+
+// blocked pass in 64 x 48 regions, 3 rows x 2 px per thread (k_iterate_tb4, gamma = 0)
+static int launch_tb4(const Level &lv, const IterArgs &a, const Pass &p, double *hbm) {
+  const BlockedPlan bp = tb4_plan(lv.lw, lv.lh, p.k);
+  TBArgs t;
+  t.it = a;
+  t.niter = p.k;
+  t.tiles_x = bp.tiles_x;
+  t.out_h = bp.out_h;
+  const int blocks = bp.blocks;
+  if (partials_fit(lv.c, blocks, blocks, "blocks") < 0) return -1;
+#define TB4_M(FM) \
+  hipLaunchKernelGGL((k_iterate_tb4<FM>), dim3(blocks), dim3(32 * kTb4Groups), 0, lv.st, t);
+  MATH_SWITCH(lv.math, TB4_M)
+#undef TB4_M
+  *hbm = blocked_hbm(blocks, kTb4Groups * kTb4RowsPerThread, (double)lv.lw * lv.lh,
+                     pass_planes(lv.gam, p.p_zero));
+  return blocks;
+}
+
+// blocked pass in 64 x 32 regions, 2 px per lane (k_iterate_tb)
+static int launch_tb(const Level &lv, const IterArgs &a, const Pass &p, double *hbm) {
+  const BlockedPlan bp = tb_plan(lv.lw, lv.lh, p.k);
+  TBArgs t;
+  t.it = a;
+  t.niter = p.k;
+  t.tiles_x = bp.tiles_x;
+  t.out_h = bp.out_h;
+  const int blocks = bp.blocks;
+  if (partials_fit(lv.c, blocks, blocks, "blocks") < 0) return -1;
+  constexpr int rh = kTbRows;
+#define TB(G, FM) \
+  hipLaunchKernelGGL((k_iterate_tb<G, rh, 1, 2, FM>), dim3(blocks), dim3(32 * rh), 0, lv.st, t);
+#define TB_M(FM) TB(false, FM)
+  if (lv.gam) {
+    TB(true, kIEEE)
+  } else {
+    MATH_SWITCH(lv.math, TB_M)
+  }
+#undef TB_M
+#undef TB
+  *hbm = blocked_hbm(blocks, rh, (double)lv.lw * lv.lh, pass_planes(lv.gam, p.p_zero));
+  return blocks;
+}
+
+// Pass kernels: 2-iteration passes (HBM-bound) stream through k_iterate_roll's x-only
+// halo; passes of >= 3 iterations are VALU-bound, where the streaming kernel wins only
+// while the level has enough rows for one round of >= 32-row segments (short segments
+// repeat the 2K-row halo) and k_iterate_tb (64 x 32 regions, 2 px/lane) wins below.
+// Planes beyond 32-bit buffer offsets take k_iterate_tb for every pass.
+// witer: the warp's first pass as k_warp_iter (storing the constants if store_c); midp: a
+// mid-check pass.  blocks_out: the residual partials of the pass (per check of a mid pass).
+static tvl1_status launch_pass(const Level &lv, const Pass &p, int wp, int n, int &blocks_out,
+                               bool witer = false, bool store_c = false, bool midp = false) {
+  tvl1_ctx *c = lv.c;
+  IterArgs a = lv.a;
+  set_planes(c, a, p.ui, p.pi, p.cb);
+  a.calc_err = p.calc_end ? 1 : 0;
+  a.p_zero = p.p_zero ? 1 : 0;
+  a.gate = p.gate;
+  a.gate_seq = p.gseq;
+  const size_t tkp = prof_begin(c, lv.st);
+  const double Nl = (double)lv.lw * lv.lh;
+  double hbm = 0.0;
+  int blocks;
+  if (witer)
+    blocks = launch_warp_iter(lv, a, p, store_c, &hbm);
+  else if (lv.exact_div)
+    blocks = launch_iterate(lv, a, p, &hbm);
+  else if (lv.roll_ok && (p.k <= 2 || lv.roll_long))
+    blocks = launch_roll(lv, a, p, midp, &hbm);
+  else if (c->tb4 && !lv.gam)
+    blocks = launch_tb4(lv, a, p, &hbm);
+  else
+    blocks = launch_tb(lv, a, p, &hbm);
+  if (blocks < 0) return TVL1_EHIP;
+  // algorithmic: 64 B/px per executed iteration (+ 40 B/px for a fused
+  // warpBackward)
+  prof_end(c, lv.st, tkp, 0, Nl * 64.0 * p.k + (witer ? Nl * 40.0 : 0.0), hbm);
+  DIAG(c, lv.st, "iteration pass", lv.s, wp, n);
+  blocks_out = blocks;
+  return TVL1_OK;
+}
+
+// the speculation gate of a check at iteration count n: gated itself on the check gin_seq (a
+// check enqueued behind another), and evaluating the prediction (pk, pcalc) for the launch
+// enqueued behind it
+static CheckGate check_gate(const tvl1_ctx *c, const Predictor &pr, int n, int pk, int pcalc,
+                            unsigned long long gin_seq, bool gated) {
+  CheckGate gt{};
+  if (gated) {
+    gt.in = c->gate;
+    gt.in_seq = gin_seq;
+  }
+  if (pk >= 0) {
+    gt.out = c->gate;
+    gt.thr = pr.scaledEps;
+    gt.n = n;
+    gt.iters = pr.iterations;
+    gt.kmax = pr.kmax;
+    gt.eps_pos = 1;
+    gt.pk = pk;
+    gt.pcalc = pcalc;
+  }
+  return gt;
+}
+
+// [A.1] convertTo + [A.2] pyramid, kernel step = float(1/scaleStep)
+static tvl1_status build_pyramid(tvl1_ctx *c, const Frames &in, int W, int H, hipStream_t st) {
+  const Geometry &g = c->geo;
+  const size_t tk = prof_begin(c, st);
+  convert_frames(c, in, W, H, st);
+  const float fdown = (float)(1.0 / c->prm.scale_step);
+  const bool contract_pyr = contracts(math_of(c->prm));
+  for (int s = 1; s < g.L; ++s) {
+    if (contract_pyr)
+      hipLaunchKernelGGL(k_resize_down2<true>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st,
+                         c->I0s[s - 1], c->I1s[s - 1], g.ws[s - 1], g.hs[s - 1], g.ps[s - 1],
+                         c->I0s[s], c->I1s[s], g.ws[s], g.hs[s], g.ps[s], fdown, fdown);
+    else
+      hipLaunchKernelGGL(k_resize_down2<false>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st,
+                         c->I0s[s - 1], c->I1s[s - 1], g.ws[s - 1], g.hs[s - 1], g.ps[s - 1],
+                         c->I0s[s], c->I1s[s], g.ws[s], g.hs[s], g.ps[s], fdown, fdown);
+  }
+  double b = (double)W * H * (2 + 8);
+  for (int s = 1; s < g.L; ++s) b += (double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8;
+  prof_end(c, st, tk, 2, b);
+  HIP_TRY(c, hipGetLastError());
+  return TVL1_OK;
+}
+
+// The flow the coarsest level starts from, in the u set *ui: 0, or the seed's coarsest level.
+// [A.2b] the seed's pyramid: u[s] = resize(u[s-1]) * scaleStep, a chain of rounded levels.
+// Only its coarsest level reaches the solver (every upsample overwrites the finer one), so
+// the first step reads the caller's planes and the steps ping-pong between the two u sets;
+// a one-level pyramid takes the seed as it is.  u3 = 0 at the coarsest level either way.
+static tvl1_status initial_flow(tvl1_ctx *c, const Seed *seed, int W, int H, hipStream_t st, int *ui_out) {
+  const Geometry &g = c->geo;
+  const int L = g.L;
+  const bool gam = g.gamma;
+  int ui = 0;
+  if (!seed) {         // u = 0 at the coarsest level (no initial flow)
+    const size_t n = (size_t)g.ps[L - 1] * g.hs[L - 1] * sizeof(float);
+    HIP_TRY(c, hipMemsetAsync(c->U[ui][0], 0, n, st));
+    HIP_TRY(c, hipMemsetAsync(c->U[ui][1], 0, n, st));
+    if (gam) HIP_TRY(c, hipMemsetAsync(c->U[ui][2], 0, n, st));
+    *ui_out = ui;
+    return TVL1_OK;
+  }
+  const float fdown = (float)(1.0 / c->prm.scale_step);
+  const float fmul = (float)c->prm.scale_step;
+  const bool contract_pyr = contracts(math_of(c->prm));
+  const size_t tk = prof_begin(c, st);
+  double b = 0.0;
+  if (L == 1) {
+    hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2), kBlk2, 0, st, seed->u0, seed->v0,
+                       (int)seed->pitch, (size_t)0, c->U[ui][0], c->U[ui][1], W, H, g.ps[0],
+                       (size_t)0);
+    b = (double)W * H * 16.0;
+  }
+  for (int s = 1; s < L; ++s) {
+    const float *s1 = s == 1 ? seed->u0 : c->U[ui][0], *s2 = s == 1 ? seed->v0 : c->U[ui][1];
+    const int sp = s == 1 ? (int)seed->pitch : g.ps[s - 1];
+    if (s > 1) ui ^= 1;
+    if (contract_pyr)
+      hipLaunchKernelGGL(k_flow_down<true>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st, s1, s2,
+                         g.ws[s - 1], g.hs[s - 1], sp, c->U[ui][0], c->U[ui][1], g.ws[s],
+                         g.hs[s], g.ps[s], fdown, fdown, fmul);
+    else
+      hipLaunchKernelGGL(k_flow_down<false>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st, s1, s2,
+                         g.ws[s - 1], g.hs[s - 1], sp, c->U[ui][0], c->U[ui][1], g.ws[s],
+                         g.hs[s], g.ps[s], fdown, fdown, fmul);
+    b += (double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8;
+  }
+  prof_end(c, st, tk, 2, b);
+  if (gam)
+    HIP_TRY(c, hipMemsetAsync(c->U[ui][2], 0, (size_t)g.ps[L - 1] * g.hs[L - 1] * sizeof(float), st));
+  HIP_TRY(c, hipGetLastError());
+  *ui_out = ui;
+  return TVL1_OK;
+}
 
 // seed: the initial flow (tvl1_calc_init), or null for u = 0 at the coarsest level
 static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W, int H, float *u,
@@ -815,395 +1233,47 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
     c->marks.clear();
   }
 
-  // [A.1] convertTo + [A.2] pyramid, kernel step = float(1/scaleStep)
-  size_t tk = prof_begin(c, st);
-  convert_frames(c, in, W, H, st);
-  const float fdown = (float)(1.0 / prm.scale_step);
-  const bool contract_pyr = contracts(math_of(prm));
-  for (int s = 1; s < L; ++s) {
-    if (contract_pyr)
-      hipLaunchKernelGGL(k_resize_down2<true>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st,
-                         c->I0s[s - 1], c->I1s[s - 1], g.ws[s - 1], g.hs[s - 1], g.ps[s - 1],
-                         c->I0s[s], c->I1s[s], g.ws[s], g.hs[s], g.ps[s], fdown, fdown);
-    else
-      hipLaunchKernelGGL(k_resize_down2<false>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st,
-                         c->I0s[s - 1], c->I1s[s - 1], g.ws[s - 1], g.hs[s - 1], g.ps[s - 1],
-                         c->I0s[s], c->I1s[s], g.ws[s], g.hs[s], g.ps[s], fdown, fdown);
-  }
-  {
-    double b = (double)W * H * (2 + 8);
-    for (int s = 1; s < L; ++s) b += (double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8;
-    prof_end(c, st, tk, 2, b);
-  }
-  HIP_TRY(c, hipGetLastError());
-
+  TVL1_TRY(build_pyramid(c, in, W, H, st));
   int ui = 0, pi = 0;  // ping-pong indices of the u and p buffer sets
   int cb = 0;          // constants buffer (I1wx, I1wy, rho) of the current warp
-  if (!seed) {         // u = 0 at the coarsest level (no initial flow)
-    const int s = L - 1;
-    const size_t n = (size_t)g.ps[s] * g.hs[s] * sizeof(float);
-    HIP_TRY(c, hipMemsetAsync(c->U[ui][0], 0, n, st));
-    HIP_TRY(c, hipMemsetAsync(c->U[ui][1], 0, n, st));
-    if (gam) HIP_TRY(c, hipMemsetAsync(c->U[ui][2], 0, n, st));
-  } else {
-    // [A.2b] the seed's pyramid: u[s] = resize(u[s-1]) * scaleStep, a chain of rounded levels.
-    // Only its coarsest level reaches the solver (every upsample overwrites the finer one), so
-    // the first step reads the caller's planes and the steps ping-pong between the two u sets;
-    // a one-level pyramid takes the seed as it is.  u3 = 0 at the coarsest level either way.
-    const float fmul = (float)prm.scale_step;
-    tk = prof_begin(c, st);
-    double b = 0.0;
-    if (L == 1) {
-      hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2), kBlk2, 0, st, seed->u0, seed->v0,
-                         (int)seed->pitch, (size_t)0, c->U[ui][0], c->U[ui][1], W, H, g.ps[0],
-                         (size_t)0);
-      b = (double)W * H * 16.0;
-    }
-    for (int s = 1; s < L; ++s) {
-      const float *s1 = s == 1 ? seed->u0 : c->U[ui][0], *s2 = s == 1 ? seed->v0 : c->U[ui][1];
-      const int sp = s == 1 ? (int)seed->pitch : g.ps[s - 1];
-      if (s > 1) ui ^= 1;
-      if (contract_pyr)
-        hipLaunchKernelGGL(k_flow_down<true>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st, s1, s2,
-                           g.ws[s - 1], g.hs[s - 1], sp, c->U[ui][0], c->U[ui][1], g.ws[s],
-                           g.hs[s], g.ps[s], fdown, fdown, fmul);
-      else
-        hipLaunchKernelGGL(k_flow_down<false>, grid2(g.ws[s], g.hs[s], 2), kBlk2, 0, st, s1, s2,
-                           g.ws[s - 1], g.hs[s - 1], sp, c->U[ui][0], c->U[ui][1], g.ws[s],
-                           g.hs[s], g.ps[s], fdown, fdown, fmul);
-      b += (double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8;
-    }
-    prof_end(c, st, tk, 2, b);
-    if (gam)
-      HIP_TRY(c, hipMemsetAsync(c->U[ui][2], 0, (size_t)g.ps[L - 1] * g.hs[L - 1] * sizeof(float), st));
-    HIP_TRY(c, hipGetLastError());
-  }
+  TVL1_TRY(initial_flow(c, seed, W, H, st, &ui));
 
-  const float l_t = (float)(prm.lambda * prm.theta);
   const float taut = (float)(prm.tau / prm.theta);
   // The projection's shared-reciprocal division (dual_px) needs ng = 1 + taut*|grad u| >= 1;
   // other parameters take the one-iteration kernel with plain IEEE divisions.
   const bool exact_div = !(taut >= 0.0f && taut <= FLT_MAX);
-  // arithmetic mode of the gamma = 0 kernels (kIEEE / kFast / kFma, tvl1_kernels.hpp);
-  // gamma != 0 and taut < 0 solves run IEEE
-  const int math = math_of(prm);
-  const float theta_f = (float)prm.theta;
-  const float gamma_f = (float)prm.gamma;
-  const float upmul = (float)(1.0 / prm.scale_step);
 
   int64_t level_iters[TVL1_MAX_LEVELS] = {};
   int64_t checks = 0;
   int32_t spec_misses = 0;   // speculative launches that ran empty
   int mid_passes = 0, mid_taken = 0;   // mid-check passes; of those, ended on the mid state
-  // share of the resident slots a streaming launch is sized for: all of them for a solve
-  // alone on its device, fill_shared while other solves are in progress (their blocks fill
-  // the rest instead of waiting for this launch's last round).  Segmentation never changes
-  // a result (tests/test_gpu_parity.py TVL1_ROLL_SEG cases)
-  auto fill_now = [&]() {
-    return g_solving[c->device & 63].load(std::memory_order_relaxed) > 1 ? c->fill_shared : c->fill;
+  // speculates only a solve alone on its device (TVL1_SPEC=2: always)
+  auto alone = [&]() {
+    return !(c->spec == 1 && g_solving[c->device & 63].load(std::memory_order_relaxed) > 1);
   };
-
-  // ---- launch helpers
-  // The streaming kernels (k_iterate_roll, k_warp_ring, k_warp_iter) take 32-bit buffer
-  // byte offsets, and the iteration passes address a whole plane group (RollBufs: up to 6
-  // planes at the level-0 plane stride) through one descriptor: a level whose largest group
-  // reaches c->buf_limit bytes uses the 64-bit-addressed kernels (k_warp_img, k_iterate_tb).
-  const size_t pstride = (size_t)g.ps[0] * g.H * sizeof(float);   // arena plane stride
-  auto group_bytes = [&](int s, int planes) {
-    return (size_t)(planes - 1) * pstride + (size_t)g.ps[s] * g.hs[s] * sizeof(float);
-  };
-  auto buffer_ok = [&](int s) { return group_bytes(s, gam ? 6 : 4) < c->buf_limit; };
-  // the planes of a pass as RollBufs groups (the arena keeps each set's planes contiguous)
-  auto roll_bufs = [&](int s, int uset, int pset, int cbuf) {
-    RollBufs b;
-    b.c = c->C[cbuf][0];
-    b.us = c->U[uset][0];
-    b.ud = c->U[uset ^ 1][0];
-    b.ps = c->Pd[pset][0];
-    b.pd = c->Pd[pset ^ 1][0];
-    b.pstride = (unsigned)pstride;
-    b.cb = (unsigned)group_bytes(s, 3);
-    b.ub = (unsigned)group_bytes(s, gam ? 3 : 2);
-    b.pb = (unsigned)group_bytes(s, gam ? 6 : 4);
-    return b;
-  };
-  auto gather = [&](int s, int uset, int cbuf, int wp) -> tvl1_status {  // K5 warpBackward
-    const int lw = g.ws[s], lh = g.hs[s], P = g.ps[s];
-    size_t t0 = prof_begin(c, st);
-    if (!buffer_ok(s)) {
-      const int tx = (lw + kWarpTW - 1) / kWarpTW, ty = (lh + kWarpTH - 1) / kWarpTH;
-#define WARP_IMG(FM)                                                                           \
-  hipLaunchKernelGGL(k_warp_img<FM>, dim3(tx * ty), dim3(256), 0, st, c->I0s[s], c->I1s[s],    \
-                     c->U[uset][0], c->U[uset][1], lw, lh, P, tx, c->C[cbuf][0], c->C[cbuf][1], \
-                     c->C[cbuf][2]);
-      MATH_SWITCH(math, WARP_IMG)
-#undef WARP_IMG
-    } else {
-      WarpRingArgs wa;
-      wa.I0 = c->I0s[s];
-      wa.I1 = c->I1s[s];
-      wa.u1 = c->U[uset][0];
-      wa.u2 = c->U[uset][1];
-      wa.I1wx = c->C[cbuf][0];
-      wa.I1wy = c->C[cbuf][1];
-      wa.rho = c->C[cbuf][2];
-      wa.W = lw;
-      wa.H = lh;
-      wa.P = P;
-      wa.bands = (lw + 63) / 64;
-      wa.seg_rows = c->roll_seg > 0 ? std::max(c->roll_seg, kRollMinSeg)
-                                    : roll_segment(wa.bands, lh, 6, c->warp_ring_slots * fill_now() / 100);
-      wa.waves = wa.bands * ((lh + wa.seg_rows - 1) / wa.seg_rows);
-#define WARP_RING(FM) \
-  hipLaunchKernelGGL((k_warp_ring<6, 2, FM>), dim3(wa.waves), dim3(128), 0, st, wa);
-      MATH_SWITCH(math, WARP_RING)
-#undef WARP_RING
-    }
-    // algorithmic: 40 B/px per warp; compulsory here ~28 B/px (I1 x 1 + 2M/64)
-    prof_end(c, st, t0, 1, (double)lw * lh * 40.0, (double)lw * lh * 28.0);
-    DIAG(c, st, "warp kernel", s, wp, -1);
-    return TVL1_OK;
-  };
-  auto upsample = [&](int s, int uset) -> tvl1_status {  // level s -> s-1 into U[uset^1]
-    const int lw = g.ws[s], lh = g.hs[s];
-    const int dw = g.ws[s - 1], dh = g.hs[s - 1];
-    const float fxu = (float)(1.0 / ((double)dw / lw));
-    const float fyu = (float)(1.0 / ((double)dh / lh));
-    size_t t0 = prof_begin(c, st);
-    if (contracts(math))
-      hipLaunchKernelGGL(k_upsample<true>, grid2(dw, dh, gam ? 3 : 2), kBlk2, 0, st, c->U[uset][0],
-                         c->U[uset][1], c->U[uset][2], lw, lh, g.ps[s], c->U[uset ^ 1][0],
-                         c->U[uset ^ 1][1], c->U[uset ^ 1][2], dw, dh, g.ps[s - 1], fxu, fyu, upmul);
-    else
-      hipLaunchKernelGGL(k_upsample<false>, grid2(dw, dh, gam ? 3 : 2), kBlk2, 0, st, c->U[uset][0],
-                         c->U[uset][1], c->U[uset][2], lw, lh, g.ps[s], c->U[uset ^ 1][0],
-                         c->U[uset ^ 1][1], c->U[uset ^ 1][2], dw, dh, g.ps[s - 1], fxu, fyu, upmul);
-    prof_end(c, st, t0, 2, (double)lw * lh * 8.0 + (double)dw * dh * 8.0);
-    DIAG(c, st, "k_upsample", s, -1, -1);
-    return TVL1_OK;
-  };
-#define TRY(expr)                      \
-  do {                                 \
-    tvl1_status r_ = (expr);           \
-    if (r_ != TVL1_OK) return r_;      \
-  } while (0)
 
   double w0_hint = 50.0;   // speculation: residual / (eps^2 W H) at a level's first check
   for (int s = L - 1; s >= 0; --s) {
     const int lw = g.ws[s], lh = g.hs[s], P = g.ps[s];
-    const double Nl = (double)lw * lh;
     const double scaledEps = prm.epsilon * prm.epsilon * (double)lw * (double)lh;
     bool p_zero = true;  // p = 0 at the start of every level (setTo(0) in procOneScale)
 
-    IterArgs a{};
-    a.W = lw;
-    a.H = lh;
-    a.P = P;
-    a.segs = (lw + kSegPx - 1) / kSegPx;
-    a.strip_rows = kStripRows;
-    a.l_t = l_t;
-    a.theta = theta_f;
-    a.gamma = gamma_f;
-    a.taut = taut;
-    a.taut_small = taut_small(taut);
-    a.partials = c->partials;
-    const int nblk = iterate_blocks(lw, lh);
-    // Pass kernels: 2-iteration passes (HBM-bound) stream through k_iterate_roll's x-only
-    // halo; passes of >= 3 iterations are VALU-bound, where the streaming kernel wins only
-    // while the level has enough rows for one round of >= 32-row segments (short segments
-    // repeat the 2K-row halo) and k_iterate_tb (64 x 32 regions, 2 px/lane) wins below.
-    // Planes beyond 32-bit buffer offsets take k_iterate_tb for every pass.
-    const bool roll_ok = buffer_ok(s);
-    const bool roll_long = roll_ok && (long)((lw + 55) / 56) * ((lh + 31) / 32) >= c->roll_long_min;
-
-    // one iteration pass of k iterations (ending in a check if calc_end) from the buffer sets
-    // (ui, pi) with the constants of set cb; witer: the warp's first pass as k_warp_iter
-    // (storing the constants if store_c).  gate: a speculative launch
-    auto launch_pass = [&](int k, bool calc_end, bool witer, bool store_c, int ui, int pi, int cb,
-                           bool p_zero, const unsigned long long *gate, unsigned long long gseq,
-                           int wp, int n, int &blocks_out, bool midp = false) -> tvl1_status {
-        a.u1s = c->U[ui][0]; a.u2s = c->U[ui][1]; a.u3s = c->U[ui][2];
-        a.u1d = c->U[ui ^ 1][0]; a.u2d = c->U[ui ^ 1][1]; a.u3d = c->U[ui ^ 1][2];
-        a.p11s = c->Pd[pi][0]; a.p12s = c->Pd[pi][1]; a.p21s = c->Pd[pi][2];
-        a.p22s = c->Pd[pi][3]; a.p31s = c->Pd[pi][4]; a.p32s = c->Pd[pi][5];
-        a.p11d = c->Pd[pi ^ 1][0]; a.p12d = c->Pd[pi ^ 1][1]; a.p21d = c->Pd[pi ^ 1][2];
-        a.p22d = c->Pd[pi ^ 1][3]; a.p31d = c->Pd[pi ^ 1][4]; a.p32d = c->Pd[pi ^ 1][5];
-        a.calc_err = calc_end ? 1 : 0;
-        a.p_zero = p_zero ? 1 : 0;
-        a.I1wx = c->C[cb][0];
-        a.I1wy = c->C[cb][1];
-        a.rho = c->C[cb][2];
-        a.gate = gate;
-        a.gate_seq = gseq;
-        int blocks = nblk;
-        const size_t tkp = prof_begin(c, st);
-        double hbm;
-        const int nu = gam ? 3 : 2, np = gam ? 6 : 4;
-        const double ld_planes = 3 + nu + (p_zero ? 0 : np), st_planes = nu + np;
-        double alg_extra = 0.0;   // the fused warpBackward's algorithmic bytes
-        if (witer) {
-          WarpIterArgs w;
-          w.ra.b = roll_bufs(s, ui, pi, cb);
-          w.ra.it = a;
-          w.ra.it.I1wx = c->C[cb][0];
-          w.ra.it.I1wy = c->C[cb][1];
-          w.ra.it.rho = c->C[cb][2];
-          w.I0 = c->I0s[s];
-          w.I1 = c->I1s[s];
-          // the constants go to HBM only when the warp may run further passes: always for
-          // a level's first warp, else when the previous warp did not stop at its first
-          // check (a wrong guess recomputes them with the warp kernel after the check)
-          w.store_c = store_c ? 1 : 0;
-          constexpr int M = kWiMargin, BW = 128;
-          w.ra.bands = (lw + BW - 5) / (BW - 4);
-          const int seg = c->roll_seg > 0 ? std::max(c->roll_seg, kRollMinSeg)
-                                          : roll_segment(w.ra.bands, lh, 2 + M, c->witer_slots * fill_now() / 100);
-          w.ra.seg_rows = seg;
-          const int segs = (lh + seg - 1) / seg;
-          w.ra.waves = w.ra.bands * segs;
-          blocks = w.ra.waves;
-          if (blocks > c->partials_cap)
-            return set_err(c, TVL1_EHIP, "internal: %d blocks > partials capacity %d", blocks,
-                           c->partials_cap);
-#define WITER(FM)                                                                           \
-  if (c->wi_nc == 2)                                                                       \
-    hipLaunchKernelGGL((k_warp_iter<M, FM, BW, 1, 2>), dim3(w.ra.waves), dim3(128 + BW),    \
-                       c->probe_wi_lds, st, w);                                             \
-  else                                                                                     \
-    hipLaunchKernelGGL((k_warp_iter<M, FM, BW, 1, 1>), dim3(w.ra.waves), dim3(64 + BW), 0, st, w);
-          MATH_SWITCH(math, WITER)
-#undef WITER
-          // compulsory: p, u, I0 and the I1 window (x 1 + 2M/BW) per band column and row;
-          // u, p (+ the constants) stored
-          double rows = 0.0;
-          for (int sg = 0; sg < segs; ++sg) {
-            const int ys = sg * seg, ye = std::min(ys + seg, lh);
-            rows += std::min(ye - 1 + 2, lh - 1) - std::max(ys - 2, 0) + 1;
-          }
-          hbm = (double)w.ra.bands * BW * rows * 4.0 *
-                    ((p_zero ? 3 : 7) + (double)wi_ww<M, BW>() / BW) +
-                Nl * 4.0 * (6.0 + (w.store_c ? 3.0 : 0.0));
-          alg_extra = Nl * 40.0;   // 40 B/px per warp
-        } else if (exact_div) {   // taut < 0 or not finite: one iteration per launch, IEEE
-          if (gam)
-            hipLaunchKernelGGL((k_iterate<true, true>), dim3(nblk), dim3(kBlock), 0, st, a);
-          else
-            hipLaunchKernelGGL((k_iterate<false, true>), dim3(nblk), dim3(kBlock), 0, st, a);
-          hbm = Nl * 4.0 * (ld_planes + st_planes) * k;
-        } else if (roll_ok && (k <= 2 || roll_long)) {
-          RollArgs ra;
-          ra.b = roll_bufs(s, ui, pi, cb);
-          ra.it = a;
-          const int px = k <= 2 && (long)lw * lh >= c->roll_px4_min ? 4 : 2;
-          const int halo = (k + px - 1) / px * px;   // roll_halo<K, PX>
-          const int out_w = 64 * px - 2 * halo;
-          ra.bands = (lw + out_w - 1) / out_w;
-          const int slots = midp ? c->mid_slots : c->roll_slots[k][gam][px];
-          const int seg = c->roll_seg > 0 ? std::max(c->roll_seg, kRollMinSeg)
-                                           : roll_segment(ra.bands, lh, k, slots * fill_now() / 100);
-          ra.seg_rows = seg;
-          const int segs = (lh + seg - 1) / seg;
-          ra.waves = ra.bands * segs;
-          blocks = ra.waves;  // one residual partial per wavefront (two for the mid pass)
-          if ((midp ? 2 : 1) * blocks > c->partials_cap)
-            return set_err(c, TVL1_EHIP, "internal: %d wavefronts > partials capacity %d", blocks,
-                           c->partials_cap);
-          if (midp && (k != 4 || px != 2 || gam || !calc_end))
-            return set_err(c, TVL1_EHIP, "internal: mid-check pass of k = %d, px = %d", k, px);
-          const dim3 grid((ra.waves + 3) / 4);
-#define ROLL_G(K, PX) \
-  hipLaunchKernelGGL((k_iterate_roll<true, K, PX>), grid, dim3(256), 0, st, ra);
-#define ROLL_M(FM, K, PX)                                                                  \
-  if (c->probe_lds > 0)                                                                    \
-    (void)hipFuncSetAttribute((const void *)k_iterate_roll<false, K, PX, FM>,              \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, c->probe_lds);   \
-  hipLaunchKernelGGL((k_iterate_roll<false, K, PX, FM>), grid, dim3(256), c->probe_lds, st, ra);
-#define ROLL(K, PX)                     \
-  if (gam) {                            \
-    ROLL_G(K, PX)                       \
-  } else if (math == kFast) {           \
-    ROLL_M(kFast, K, PX)                \
-  } else if (math == kFma) {            \
-    ROLL_M(kFma, K, PX)                 \
-  } else {                              \
-    ROLL_M(kIEEE, K, PX)                \
-  }
-#define MID_M(FM) hipLaunchKernelGGL((k_iterate_roll_mid<FM>), grid, dim3(256), 0, st, ra);
-          if (midp) {
-            MATH_SWITCH(math, MID_M)
-          } else if (px == 4) {   // k <= 2
-            if (k == 1) {
-              ROLL(1, 4)
-            } else {
-              ROLL(2, 4)
-            }
-          } else {
-            switch (k) {
-              case 1: ROLL(1, 2) break;
-              case 2: ROLL(2, 2) break;
-              case 3: ROLL(3, 2) break;
-              default: ROLL(4, 2) break;
-            }
-          }
-#undef MID_M
-#undef ROLL
-#undef ROLL_M
-#undef ROLL_G
-          // compulsory: every band lane loads its column over the segment's rows + halo
-          double rows = 0.0;
-          for (int sg = 0; sg < segs; ++sg) {
-            const int ys = sg * seg, ye = std::min(ys + seg, lh);
-            rows += std::min(ye - 1 + k, lh - 1) - std::max(ys - k, 0) + 1;
-          }
-          hbm = (double)ra.bands * 64.0 * px * rows * 4.0 * ld_planes + Nl * 4.0 * st_planes;
-        } else if (c->tb4 && !gam) {   // 64 x 48 regions, 3 rows x 2 px per thread
-          TBArgs t;
-          t.it = a;
-          t.niter = k;
-          t.tiles_x = (lw + 55) / 56;
-          constexpr int nr = kTb4RowsPerThread;
-          t.out_h = kTb4Groups * nr - 2 * k;
-          blocks = t.tiles_x * ((lh + t.out_h - 1) / t.out_h);
-          if (blocks > c->partials_cap)
-            return set_err(c, TVL1_EHIP, "internal: %d blocks > partials capacity %d", blocks,
-                           c->partials_cap);
-#define TB4_M(FM) \
-  hipLaunchKernelGGL((k_iterate_tb4<FM>), dim3(blocks), dim3(32 * kTb4Groups), 0, st, t);
-          MATH_SWITCH(math, TB4_M)
-#undef TB4_M
-          hbm = (double)blocks * 64.0 * (kTb4Groups * nr) * 4.0 * ld_planes + Nl * 4.0 * st_planes;
-        } else {   // 64 x 32 regions, 2 px per lane
-          TBArgs t;
-          t.it = a;
-          t.niter = k;
-          t.tiles_x = (lw + 55) / 56;
-          constexpr int rh = 32;
-          t.out_h = rh - 2 * k;
-          blocks = t.tiles_x * ((lh + t.out_h - 1) / t.out_h);
-          if (blocks > c->partials_cap)
-            return set_err(c, TVL1_EHIP, "internal: %d blocks > partials capacity %d", blocks,
-                           c->partials_cap);
-#define TB(G, FM) \
-  hipLaunchKernelGGL((k_iterate_tb<G, rh, 1, 2, FM>), dim3(blocks), dim3(32 * rh), 0, st, t);
-#define TB_M(FM) TB(false, FM)
-          if (gam) {
-            TB(true, kIEEE)
-          } else {
-            MATH_SWITCH(math, TB_M)
-          }
-#undef TB_M
-#undef TB
-          // compulsory for this tiling: every staged region cell loads I1wx, I1wy, rho,
-          // u (+p unless p == 0), every px stores u and p once per pass
-          hbm = (double)blocks * 64.0 * rh * 4.0 * ld_planes + Nl * 4.0 * st_planes;
-        }
-        // algorithmic: 64 B/px per executed iteration (+ 40 B/px for a
-        // fused warpBackward)
-        prof_end(c, st, tkp, 0, Nl * 64.0 * k + alg_extra, hbm);
-        DIAG(c, st, "iteration pass", s, wp, n);
-        blocks_out = blocks;
-        return TVL1_OK;
-    };
+    Level lv{};
+    lv.c = c;
+    lv.st = st;
+    lv.s = s;
+    lv.lw = lw;
+    lv.lh = lh;
+    lv.P = P;
+    lv.a = iter_args(prm, lw, lh, P, c->partials);
+    // arithmetic mode of the gamma = 0 kernels (kIEEE / kFast / kFma, tvl1_kernels.hpp);
+    // gamma != 0 and taut < 0 solves run IEEE
+    lv.math = math_of(prm);
+    lv.gam = gam;
+    lv.exact_div = exact_div;
+    lv.roll_ok = buffer_ok(c, s);
+    lv.roll_long = lv.roll_ok && (long)((lw + 55) / 56) * ((lh + 31) / 32) >= c->roll_long_min;
+    const bool roll_ok = lv.roll_ok;
 
     // warpBackward fused into the warp's first pass (2 iterations ending in the first
     // check) when that pass would stream through k_iterate_roll anyway
@@ -1211,99 +1281,16 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
                       prm.iterations >= 2 && (long)lw * lh >= c->fuse_min;
     const int kmax = exact_div ? 1 : roll_ok ? kRollMax : kTbMax;
     // the mid-check pass (k_iterate_roll_mid) where a 4-iteration pass streams
-    const bool mid_ok = !gam && !exact_div && roll_long && prm.epsilon > 0 && kRollMax >= 4;
+    const bool mid_ok = !gam && !exact_div && lv.roll_long && prm.epsilon > 0 && kRollMax >= 4;
     // Speculation: behind each residual check the host enqueues the launch it
     // expects to follow, gated on the device by the check's own evaluation of the stopping
     // rule, and only then waits for the residual.  A right guess hides the host round trip;
     // a wrong one costs an empty launch, and the host enqueues the right work as before.
     const bool spec_ok = c->spec && !exact_div && roll_ok && prm.epsilon > 0;
     const bool spec_stop_ok = spec_ok && !median && prm.iterations >= 2;
-    // Guesses.  A warp's residual (in units of eps^2 W H) after its first check falls steadily,
-    // so: the action the level's previous warp took at the same iteration count; else the
-    // next residual extrapolated from the last two (the check after a long run of unchecked
-    // iterations comes where the schedule's linear model crosses 1: guess a stop); a level's
-    // first warp starts where the previous level's did.
-    struct Hist {
-      double r0 = -1.0, r1 = -1.0;   // the warp's last two residuals / (eps^2 W H); < 0: none
-      int n0 = -1, n_last = -1;      // iteration counts at those checks
-    };
-    // the residual expected at the check after one at n (the warp's history up to that check)
-    auto extrapolate = [&](const Hist &h, int n, int wp) {
-      if (h.r1 < 0) return wp == 0 ? w0_hint : 1.5;
-      if (n - h.n_last > 2) return 0.9;   // a long unchecked run ends near the model's crossing
-      if (h.r0 >= 0 && h.n_last - h.n0 == 2) return h.r1 * (h.r1 / h.r0);   // steady decay
-      return h.n_last == 2 ? h.r1 * 0.6 : h.r1 * 0.93;   // after a warp's first check: a drop
-    };
-    // (remembered up to 4096 iterations: a huge `iterations` must not size a huge table)
-    const size_t nact = (size_t)std::min(prm.iterations, 4096) + 1;
-    std::vector<int> act_prev(nact, -2), act_cur(nact, -2);
-    auto act_of = [&](double e, int n) {   // 0: stop, else k << 1 | calc_end
-      if (!(e > scaledEps && n < prm.iterations)) return 0;
-      bool ce;
-      double pe;
-      return sched_after(e, scaledEps, n, prm.iterations, kmax, 1, &ce, &pe) << 1 | (ce ? 1 : 0);
-    };
-    // what to predict after a check at iteration count n of warp wp: pk = 0 the warp stops
-    // (its successor's first pass follows), pk > 0 it continues with (pk, pcalc), -1 nothing
-    auto predict0 = [&](int wp, int n, bool nostore, int last_n, const Hist &h,
-                        const std::vector<int> *prevw, int &pk, int &pcalc) {
-      pk = -1;
-      pcalc = 0;
-      if (!spec_ok) return;
-      if (c->spec == 1 && g_solving[c->device & 63].load(std::memory_order_relaxed) > 1) return;
-      const bool can_stop = spec_stop_ok && wp + 1 < prm.warps;
-      const bool can_cont = !nostore && n < prm.iterations;
-      if (can_stop && (n >= prm.iterations || (n == 2 && last_n == 2))) {
-        pk = 0;
-        return;
-      }
-      const int ap = prevw && wp >= 2 && n < (int)prevw->size() ? (*prevw)[n] : -2;
-      if (ap == 0 && can_stop) {
-        pk = 0;
-        return;
-      }
-      if (ap > 0 && can_cont) {
-        pk = ap >> 1;
-        pcalc = ap & 1;
-        return;
-      }
-      const double r = extrapolate(h, n, wp);
-      if (r <= 1.0 && can_stop) {
-        pk = 0;
-      } else if (can_cont) {
-        const int a = act_of(std::max(r, 1.0 + 1e-9) * scaledEps, n);
-        pk = a >> 1;
-        pcalc = a & 1;
-      } else if (can_stop) {
-        pk = 0;
-      }
-    };
-    // a predicted 2-iteration continuation after a warp's first check is left to the host,
-    // which may run it as a mid-check pass (less GPU work than the pass enqueued ahead)
-    auto predict = [&](int wp, int n, bool nostore, int last_n, const Hist &h,
-                       const std::vector<int> *prevw, int &pk, int &pcalc) {
-      predict0(wp, n, nostore, last_n, h, prevw, pk, pcalc);
-      if (c->mid && mid_ok && pk == 2 && pcalc && n > 2) pk = -1;
-    };
-    auto gate_of = [&](int wp, int n, int pk, int pcalc, unsigned long long gin_seq, bool gated) {
-      CheckGate gt{};
-      if (gated) {
-        gt.in = c->gate;
-        gt.in_seq = gin_seq;
-      }
-      if (pk >= 0) {
-        gt.out = c->gate;
-        gt.thr = scaledEps;
-        gt.n = n;
-        gt.iters = prm.iterations;
-        gt.kmax = kmax;
-        gt.eps_pos = 1;
-        gt.pk = pk;
-        gt.pcalc = pcalc;
-      }
-      (void)wp;
-      return gt;
-    };
+    Predictor pred(prm.iterations, kmax, scaledEps, prm.warps, spec_ok, spec_stop_ok,
+                   c->mid && mid_ok, w0_hint);
+    using Hist = Predictor::Hist;
 
     int last_warp_n = -1;   // iterations of the level's previous warp
     // a warp whose first pass (and check) the previous warp enqueued speculatively
@@ -1339,11 +1326,8 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
           }
           ui ^= 1;
         }
-        if (!fuse) TRY(gather(s, ui, cb, wp));
+        if (!fuse) TVL1_TRY(gather(lv, ui, cb, wp));
       }
-      a.I1wx = c->C[cb][0];
-      a.I1wy = c->C[cb][1];
-      a.rho = c->C[cb][2];
       bool next_pre = false;   // this warp stopped where predicted: the next warp has begun
       while (pending || (error > scaledEps && n < prm.iterations)) {
         if (!pending) {
@@ -1362,22 +1346,16 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
           if (c->mid && mid_ok && k == 2 && calc_end && n > 2 && n + 4 <= prm.iterations &&
               prevError >= c->mid_min * scaledEps) {
             int blocks = 0;
-            TRY(launch_pass(4, true, false, false, ui, pi, cb, p_zero, nullptr, 0, wp, n, blocks, true));
+            TVL1_TRY(launch_pass(lv, Pass{4, true, ui, pi, cb, p_zero, nullptr, 0}, wp, n, blocks, false,
+                                 false, true));
             unsigned long long seq_mid = 0, seq_end = 0;
-            TRY(launch_check(c, st, blocks, CheckGate{}, &seq_mid, blocks));
-            TRY(launch_check(c, st, blocks, CheckGate{}, &seq_end));
-            auto note = [&](double e, int nn) {   // the bookkeeping of a check read below
-              ++checks;
-              h.r0 = h.r1;
-              h.n0 = h.n_last;
-              h.r1 = e / scaledEps;
-              h.n_last = nn;
-              if ((size_t)nn < nact) act_cur[nn] = act_of(e, nn);
-            };
+            TVL1_TRY(launch_check(c, st, blocks, CheckGate{}, &seq_mid, blocks));
+            TVL1_TRY(launch_check(c, st, blocks, CheckGate{}, &seq_end));
             double e_mid = 0.0;
-            TRY(wait_check(c, st, seq_mid, &e_mid));
+            TVL1_TRY(wait_check(c, st, seq_mid, &e_mid));
             n += 2;
-            note(e_mid, n);
+            ++checks;
+            pred.note(h, e_mid, n);
             ++mid_passes;
             bool ce2 = false;
             double prev2 = 0.0;
@@ -1385,14 +1363,15 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
             if (!stop &&
                 sched_after(e_mid, scaledEps, n, prm.iterations, kmax, 1, &ce2, &prev2) == 2 && ce2) {
               double e_end = 0.0;   // the second check: the next pass's own
-              TRY(wait_check(c, st, seq_end, &e_end));
+              TVL1_TRY(wait_check(c, st, seq_end, &e_end));
               n += 2;
-              note(e_end, n);
+              ++checks;
+              pred.note(h, e_end, n);
               error = e_end;
               prevError = e_end;
             } else {   // the state at the first check: its 2 iterations again, no residual
               ++mid_taken;
-              TRY(launch_pass(2, false, false, false, ui, pi, cb, false, nullptr, 0, wp, n - 2, blocks));
+              TVL1_TRY(launch_pass(lv, Pass{2, false, ui, pi, cb, false, nullptr, 0}, wp, n - 2, blocks));
               error = e_mid;
               prevError = e_mid;
             }
@@ -1407,7 +1386,8 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
           // check (a wrong guess recomputes them with the warp kernel after the check)
           const bool store_c = wp == 0 || last_warp_n != 2;
           int blocks = 0;
-          TRY(launch_pass(k, calc_end, witer, store_c, ui, pi, cb, p_zero, nullptr, 0, wp, n, blocks));
+          TVL1_TRY(launch_pass(lv, Pass{k, calc_end, ui, pi, cb, p_zero, nullptr, 0}, wp, n, blocks, witer,
+                               store_c));
           if (witer) fused_nostore = !store_c;
           p_zero = false;
           ui ^= 1;
@@ -1418,8 +1398,9 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
             prevError = prev_sim;
             continue;
           }
-          predict(wp, n, fused_nostore, last_warp_n, h, &act_prev, pend_pk, pend_pcalc);
-          TRY(launch_check(c, st, blocks, gate_of(wp, n, pend_pk, pend_pcalc, 0, false), &pend_seq));
+          pred.predict(wp, n, alone(), fused_nostore, last_warp_n, h, false, pend_pk, pend_pcalc);
+          TVL1_TRY(launch_check(c, st, blocks, check_gate(c, pred, n, pend_pk, pend_pcalc, 0, false),
+                                &pend_seq));
         }
         pending = false;
         // the predicted launch(es) behind the check, gated on it
@@ -1435,37 +1416,35 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
           int blocks = 0;
           // the gather is not gated (a gate check costs k_warp_ring 34 VGPRs): after a wrong
           // guess it has only filled the constants set the next warp recomputes anyway
-          if (!fuse) TRY(gather(s, ui, cb2, w2));
-          TRY(launch_pass(2, true, fuse, store2, ui, pi, cb2, false, c->gate, pend_seq, w2, 0, blocks));
+          if (!fuse) TVL1_TRY(gather(lv, ui, cb2, w2));
+          TVL1_TRY(launch_pass(lv, Pass{2, true, ui, pi, cb2, false, c->gate, pend_seq}, w2, 0, blocks, fuse,
+                               store2));
           sp_nostore = fuse && !store2;
-          if ((size_t)n < nact) act_cur[n] = 0;   // (as guessed; recorded after the read)
-          predict(w2, 2, sp_nostore, n, Hist{}, &act_cur, sp_pk2, sp_pcalc2);
-          TRY(launch_check(c, st, blocks, gate_of(w2, 2, sp_pk2, sp_pcalc2, pend_seq, true), &sp_seq));
+          pred.note_stop_guess(n);   // (as guessed; recorded after the read)
+          pred.predict(w2, 2, alone(), sp_nostore, n, Hist{}, true, sp_pk2, sp_pcalc2);
+          TVL1_TRY(launch_check(c, st, blocks, check_gate(c, pred, 2, sp_pk2, sp_pcalc2, pend_seq, true),
+                                &sp_seq));
         } else if (sp_pk > 0) {   // this warp's next pass
           int blocks = 0;
-          TRY(launch_pass(sp_pk, sp_pcalc != 0, false, false, ui, pi, cb, false, c->gate, pend_seq,
-                          wp, n, blocks));
+          TVL1_TRY(launch_pass(lv, Pass{sp_pk, sp_pcalc != 0, ui, pi, cb, false, c->gate, pend_seq}, wp, n,
+                               blocks));
           if (sp_pcalc) {
             Hist h2;   // with check j's residual extrapolated
             h2.r0 = h.r1;
             h2.n0 = h.n_last;
-            h2.r1 = h.r1 < 0 ? -1.0 : extrapolate(h, n, wp);
+            h2.r1 = h.r1 < 0 ? -1.0 : pred.extrapolate(h, n, wp);
             h2.n_last = n;
-            predict(wp, n + sp_pk, false, last_warp_n, h2, &act_prev, sp_pk2, sp_pcalc2);
-            TRY(launch_check(c, st, blocks, gate_of(wp, n + sp_pk, sp_pk2, sp_pcalc2, pend_seq, true),
-                             &sp_seq));
+            pred.predict(wp, n + sp_pk, alone(), false, last_warp_n, h2, false, sp_pk2, sp_pcalc2);
+            TVL1_TRY(launch_check(c, st, blocks,
+                                  check_gate(c, pred, n + sp_pk, sp_pk2, sp_pcalc2, pend_seq, true), &sp_seq));
           }
         }
-        TRY(wait_check(c, st, pend_seq, &error));   // the cuda::sum -> host read
+        TVL1_TRY(wait_check(c, st, pend_seq, &error));   // the cuda::sum -> host read
         prevError = error;
         ++checks;
         const bool ends = !(error > scaledEps && n < prm.iterations);
-        if (wp == 0 && h.r1 < 0) w0_hint = error / scaledEps;
-        h.r0 = h.r1;
-        h.n0 = h.n_last;
-        h.r1 = error / scaledEps;
-        h.n_last = n;
-        if ((size_t)n < nact) act_cur[n] = act_of(error, n);
+        if (wp == 0 && h.r1 < 0) w0_hint = pred.w0_hint = error / scaledEps;
+        pred.note(h, error, n);
         bool right = false;
         double sp_prev = 0.0;
         if (sp_pk == 0) {
@@ -1513,7 +1492,7 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
         }
         // k_warp_iter guessed that this warp stops here; it continues: compute its
         // constants (from its input u, the set the pass just read) before the next pass
-        if (fused_nostore && !ends) TRY(gather(s, ui ^ 1, cb, wp));
+        if (fused_nostore && !ends) TVL1_TRY(gather(lv, ui ^ 1, cb, wp));
         fused_nostore = false;
       }
       level_iters[s] += n;
@@ -1522,57 +1501,23 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
         stats->warp_iterations[s * prm.warps + wp] = n;
       cb ^= 1;  // every warp gets the other constants buffer
       pre = next_pre;
-      act_prev.swap(act_cur);
-      std::fill(act_cur.begin(), act_cur.end(), -2);
+      pred.next_warp();
     }
     HIP_TRY(c, hipGetLastError());
     if (s == 0) break;
-    TRY(upsample(s, ui));  // zoom the flow to level s-1, scale by 1/scaleStep
+    TVL1_TRY(upsample(lv, ui));  // zoom the flow to level s-1, scale by 1/scaleStep
     ui ^= 1;
   }
-#undef TRY
-  tk = prof_begin(c, st);
+  const size_t tk = prof_begin(c, st);
   hipLaunchKernelGGL(k_output, grid2(W, H), kBlk2, 0, st, c->U[ui][0], c->U[ui][1], W, H,
                      g.ps[0], u, v, fpitch);
   prof_end(c, st, tk, 2, (double)W * H * 16.0);
   HIP_TRY(c, hipGetLastError());
 
-  if (stats) {
-    for (int k = 0; k < 4; ++k) {
-      stats->kernel_ms[k] = 0.0;
-      stats->kernel_launches[k] = 0;
-      stats->kernel_bytes[k] = 0.0;
-      stats->kernel_hbm_bytes[k] = 0.0;
-    }
-  }
-  if (c->profiling && !c->marks.empty()) {
-    HIP_TRY(c, hipEventSynchronize(c->ev_pool[c->marks.back().b]));
-    for (const auto &m : c->marks) {
-      float ms = 0.f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_pool[m.a], c->ev_pool[m.b]));
-      if (stats) {
-        stats->kernel_ms[m.cls] += ms;
-        stats->kernel_launches[m.cls] += 1;
-        stats->kernel_bytes[m.cls] += m.bytes;
-        stats->kernel_hbm_bytes[m.cls] += m.hbm_bytes;
-      }
-    }
-  }
-
-  if (stats) {
-    stats->levels = L;
-    int64_t tot = 0;
-    for (int s = 0; s < TVL1_MAX_LEVELS; ++s) {
-      stats->level_width[s] = s < L ? g.ws[s] : 0;
-      stats->level_height[s] = s < L ? g.hs[s] : 0;
-      stats->level_iterations[s] = s < L ? level_iters[s] : 0;
-      tot += s < L ? level_iters[s] : 0;
-    }
-    stats->iterations_total = tot;
-    stats->checks_total = checks;
-    stats->speculation_misses = spec_misses;
-    stats->algorithmic_bytes = survey_bytes(g, prm.warps, level_iters);
-  }
+  ClassTotals tot;
+  if (stats) fill_stats(stats, g, prm.warps, level_iters, checks, spec_misses);
+  TVL1_TRY(sum_marks(c, tot));
+  if (stats) put_class_totals(stats, tot);
   if (c->spec_trace && mid_passes)
     fprintf(stderr, "mid-check passes %d, ended on the mid state %d\n", mid_passes, mid_taken);
   return TVL1_OK;
@@ -1594,9 +1539,7 @@ static tvl1_status ensure_batch(tvl1_ctx *c, int W, int H, int n, hipStream_t st
     return TVL1_OK;
   const size_t P0 = (size_t)g.ps[0];
   const size_t ps = align_up(P0 * H, 64);
-  // residual partials per pair: blocked regions (56 x 24 px) or rolling / fused waves
-  // (>= 56-px bands x >= 8-row segments)
-  const int tb_blocks = std::max(((W + 55) / 56) * ((H + 23) / 24), ((W + 55) / 56) * ((H + 7) / 8)) + 64;
+  const int tb_blocks = batch_partials_capacity(W, H);   // residual partials per pair
   size_t bytes = 0;
   size_t ips[TVL1_MAX_LEVELS];
   for (int s = 0; s < g.L; ++s) {
@@ -1641,6 +1584,308 @@ static tvl1_status ensure_batch(tvl1_ctx *c, int W, int H, int n, hipStream_t st
   return TVL1_OK;
 }
 
+// ---- batched launchers
+// What the batched launchers need of one level of a chunk of n pairs
+struct BatchLevel {
+  tvl1_ctx *c;
+  hipStream_t st;
+  int n;
+  int s, lw, lh, P;
+  int math;
+  size_t ps;         // pair stride of the level-0-sized planes (floats)
+  RollBufs bufs;     // RollBufs geometry of the batch arena (the kernels point it at each pair's planes)
+  IterArgs it;       // pass geometry and scalars (plane pointers are set per pair)
+};
+
+// [A.1] convertTo + [A.2] pyramid of every pair
+static void batch_pyramid(tvl1_ctx *c, int n, const uint8_t *I0, size_t pitch0, size_t stride0,
+                          const uint8_t *I1, size_t pitch1, size_t stride1, int W, int H, hipStream_t st) {
+  const Geometry &g = c->geo;
+  hipLaunchKernelGGL(kb_convert, grid2(W, H, 2 * n), kBlk2, 0, st, I0, pitch0, stride0, I1,
+                     pitch1, stride1, c->bI0s[0], c->bI1s[0], W, H, g.ps[0], c->bips[0]);
+  const float fdown = (float)(1.0 / c->prm.scale_step);
+  const bool contract = contracts(math_of(c->prm));
+  for (int s = 1; s < g.L; ++s) {
+#define KB_DOWN(C)                                                                             \
+  hipLaunchKernelGGL(kb_resize_down2<C>, grid2(g.ws[s], g.hs[s], 2 * n), kBlk2, 0, st,         \
+                     c->bI0s[s - 1], c->bI1s[s - 1], g.ws[s - 1], g.hs[s - 1], g.ps[s - 1],    \
+                     c->bips[s - 1], c->bI0s[s], c->bI1s[s], g.ws[s], g.hs[s], g.ps[s],       \
+                     c->bips[s], fdown, fdown);
+    if (contract) {
+      KB_DOWN(true)
+    } else {
+      KB_DOWN(false)
+    }
+#undef KB_DOWN
+  }
+}
+
+// The flow the coarsest level starts from, in set 0 of every pair: 0, or
+// [A.2b] every pair's seed pyramid (solve()'s chain): the first step reads the caller's
+// planes, the steps alternate between the u sets and the last one writes set 0
+static tvl1_status batch_initial_flow(tvl1_ctx *c, int n, const Seed *seed, int W, int H, hipStream_t st) {
+  const Geometry &g = c->geo;
+  const int L = g.L;
+  const size_t ps = c->bps;
+  if (!seed) {   // u = 0 at the coarsest level, set 0 of every pair
+    for (int k = 0; k < 2; ++k)
+      HIP_TRY(c, hipMemsetAsync(c->bU[0][k], 0, ps * n * sizeof(float), st));
+    return TVL1_OK;
+  }
+  const float fdown = (float)(1.0 / c->prm.scale_step);
+  const float fmul = (float)c->prm.scale_step;
+  const bool contract = contracts(math_of(c->prm));
+  const size_t tkf = prof_begin(c, st);
+  double fb = 0.0;
+  if (L == 1) {
+    hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2 * n), kBlk2, 0, st, seed->u0, seed->v0,
+                       (int)seed->pitch, seed->stride, c->bU[0][0], c->bU[0][1], W, H, g.ps[0], ps);
+    fb = (double)n * W * H * 16.0;
+  }
+  int set = L & 1;   // L - 1 steps end in set 0
+  for (int s = 1; s < L; ++s, set ^= 1) {
+    const float *s1 = s == 1 ? seed->u0 : c->bU[set ^ 1][0], *s2 = s == 1 ? seed->v0 : c->bU[set ^ 1][1];
+    const int sp = s == 1 ? (int)seed->pitch : g.ps[s - 1];
+    const size_t sps = s == 1 ? seed->stride : ps;
+#define KB_FLOW(C)                                                                             \
+  hipLaunchKernelGGL(kb_flow_down<C>, grid2(g.ws[s], g.hs[s], 2 * n), kBlk2, 0, st, s1, s2,    \
+                     g.ws[s - 1], g.hs[s - 1], sp, sps, c->bU[set][0], c->bU[set][1], g.ws[s], \
+                     g.hs[s], g.ps[s], ps, fdown, fdown, fmul);
+    if (contract) {
+      KB_FLOW(true)
+    } else {
+      KB_FLOW(false)
+    }
+#undef KB_FLOW
+    fb += (double)n * ((double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8);
+  }
+  prof_end(c, st, tkf, 2, fb);
+  return TVL1_OK;
+}
+
+// The coarsest level on chip (kb_small_level, one workgroup per pair: every warp's gather,
+// iterations, residuals and stopping rule without leaving the workgroup); u enters as 0 (or,
+// seeded, as set 0's planes: <FM, true>) and leaves in set 0.  Reads back every pair's
+// iterations per warp and checks: hw[b * warps + wp], then hw[n * warps + b].
+static tvl1_status batch_small_level(const BatchLevel &bl, const BatchSel &all, bool seeded,
+                                     double scaledEps, std::vector<int> &hw) {
+  tvl1_ctx *c = bl.c;
+  hipStream_t st = bl.st;
+  const tvl1_params &prm = c->prm;
+  const int n = bl.n, lw = bl.lw, lh = bl.lh;
+  const size_t need = (size_t)n * (prm.warps + 1) * sizeof(int);
+  if (need > c->small_bytes)
+    TVL1_TRY(arena_alloc(c, &c->small_scratch, &c->small_bytes, std::max<size_t>(need, 64 << 10), st));
+  BatchSmall sm{};
+  sm.I0 = c->bI0s[bl.s];
+  sm.I1 = c->bI1s[bl.s];
+  sm.u1 = c->bU[0][0];
+  sm.u2 = c->bU[0][1];
+  sm.ips = c->bips[bl.s];
+  sm.ps = bl.ps;
+  sm.W = lw;
+  sm.H = lh;
+  sm.P = bl.P;
+  sm.warps = prm.warps;
+  sm.iterations = prm.iterations;
+  sm.eps_pos = prm.epsilon > 0;
+  sm.thr = scaledEps;
+  sm.it = bl.it;
+  sm.warp_iters = reinterpret_cast<int *>(c->small_scratch);
+  sm.checks = sm.warp_iters + (size_t)n * prm.warps;
+  sm.sel = all;
+  const size_t tks = prof_begin(c, st);
+#define KB_SMALL(FM)                                                                               \
+  if (seeded)                                                                                     \
+    hipLaunchKernelGGL((kb_small_level<FM, true>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm); \
+  else                                                                                            \
+    hipLaunchKernelGGL((kb_small_level<FM>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm);
+  MATH_SWITCH(bl.math, KB_SMALL)
+#undef KB_SMALL
+  HIP_TRY(c, hipGetLastError());
+  hw.resize((size_t)n * (prm.warps + 1));
+  HIP_TRY(c, hipMemcpyAsync(hw.data(), c->small_scratch, need, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  int64_t it_sum = 0;
+  for (size_t i = 0; i < (size_t)n * prm.warps; ++i) it_sum += hw[i];
+  // its own class (3): SURVEY 8(d)'s bytes of every iteration and warp it ran, but from HBM
+  // it only reads I0, I1 and writes u once, so it would skew class 0's HBM roofline
+  prof_end(c, st, tks, 3, (double)lw * lh * (64.0 * it_sum + 40.0 * n * prm.warps),
+           (double)lw * lh * 16.0 * n);
+  return TVL1_OK;
+}
+
+static int batch_partials_fit(tvl1_ctx *c, int blocks, const char *what) {
+  if (blocks <= c->bnblk) return blocks;
+  (void)set_err(c, TVL1_EHIP, "internal: %d %s > batch partials %d", blocks, what, c->bnblk);
+  return -1;
+}
+
+// warpBackward fused with the warp's first pass (kb_warp_iter) for the pairs of sel, nstore
+// of which store their constants.  Returns the residual partials per pair (-1: error set).
+static int launch_batch_warp_iter(const BatchLevel &bl, const BatchSel &sel, int nstore) {
+  tvl1_ctx *c = bl.c;
+  hipStream_t st = bl.st;
+  const int n = bl.n;
+  const StreamPlan sp = plan_warp_iter(bl.lw, bl.lh, 128, 6, c->witer_slots, 0, n);
+  if (batch_partials_fit(c, sp.waves, "blocks") < 0) return -1;
+  BatchWI wi{};
+  wi.w.ra.b = bl.bufs;
+  wi.w.ra.it = bl.it;
+  wi.w.ra.bands = sp.bands;
+  wi.w.ra.seg_rows = sp.seg_rows;
+  wi.w.ra.waves = sp.waves;
+  wi.I0 = c->bI0s[bl.s];
+  wi.I1 = c->bI1s[bl.s];
+  set_batch_upc(c, wi);
+  wi.ips = c->bips[bl.s];
+  wi.ps = bl.ps;
+  wi.partials = c->bpartials;
+  wi.nblk = sp.waves;
+  wi.sel = sel;
+  const size_t tkw = prof_begin(c, st);
+#define KB_WITER(FM)                                                                             \
+  if (c->wi_nc == 2)                                                                            \
+    hipLaunchKernelGGL((kb_warp_iter<6, FM, 2>), dim3(wi.w.ra.waves, n), dim3(256), 0, st, wi); \
+  else                                                                                          \
+    hipLaunchKernelGGL((kb_warp_iter<6, FM, 1>), dim3(wi.w.ra.waves, n), dim3(192), 0, st, wi);
+  MATH_SWITCH(bl.math, KB_WITER)
+#undef KB_WITER
+  if (tkw) {   // k_warp_iter's accounting per pair (constants always stored), x n
+    const double Nl = (double)bl.lw * bl.lh;
+    int nz = 0;   // pairs whose p is zero (a level's first warp): p not loaded
+    for (int b = 0; b < n; ++b) nz += sel.pzero.test(b) ? 1 : 0;
+    prof_end(c, st, tkw, 0, (double)n * Nl * (64.0 * 2 + 40.0),
+             batch_warp_iter_hbm(sp, bl.lh, wi_ww<6, 128>(), Nl, n, nz, nstore));
+  }
+  return sp.waves;
+}
+
+// k_warp_ring's streaming LDS-ring gather for the pairs of sel (a warp's gather of every pair,
+// or the regather of the pairs whose fused pass did not store the constants they now need)
+static void launch_batch_ring(const BatchLevel &bl, const BatchSel &sel) {
+  tvl1_ctx *c = bl.c;
+  hipStream_t st = bl.st;
+  const int lw = bl.lw, lh = bl.lh;
+  const StreamPlan sp = plan_warp_ring(lw, lh, 6, c->warp_ring_slots, 0, sel.n);
+  BatchRing br{};
+  br.wa.W = lw;
+  br.wa.H = lh;
+  br.wa.P = bl.P;
+  br.wa.bands = sp.bands;
+  br.wa.seg_rows = sp.seg_rows;
+  br.wa.waves = sp.waves;
+  br.I0 = c->bI0s[bl.s];
+  br.I1 = c->bI1s[bl.s];
+  set_batch_uc(c, br);
+  br.ips = c->bips[bl.s];
+  br.ps = bl.ps;
+  br.sel = sel;
+  const size_t tkr = prof_begin(c, st);
+#define KB_RING(FM) \
+  hipLaunchKernelGGL((kb_warp_ring<6, 2, FM>), dim3(br.wa.waves, sel.n), dim3(128), 0, st, br);
+  MATH_SWITCH(bl.math, KB_RING)
+#undef KB_RING
+  prof_end(c, st, tkr, 1, (double)sel.n * lw * lh * 40.0, (double)sel.n * lw * lh * 28.0);
+}
+
+// One pass group: K iterations for the pairs of sel (kb_iterate_roll: wavefront pipelines,
+// 64*PX-px bands down the whole level, one per wave).  Returns the residual partials per pair
+// (pair stride c->bnblk; -1: error set).
+static int launch_batch_roll(const BatchLevel &bl, int K, const BatchSel &sel) {
+  tvl1_ctx *c = bl.c;
+  hipStream_t st = bl.st;
+  const int lw = bl.lw, lh = bl.lh, math = bl.math;
+  // PX = 1 (64-px bands) on narrow levels when TVL1_BATCH_PX1_W asks for it
+  const int px = lw <= c->batch_px1_w ? 1 : 2;
+  // segments sized so the launch's wavefronts fill whole rounds of resident slots,
+  // but never shorter than min(rows, batch_seg_min): a pass group of a few pairs (or
+  // a tiny level) would otherwise be cut into short segments that repeat the 2K-row
+  // halo to fill slots the other batch in flight fills anyway (r5: one segment per
+  // band on the strips' <= 100-row levels, +1.7 % strip solves/s,
+  // profiles/r5/ab/strips_seg/)
+  const StreamPlan sp = plan_roll(lw, lh, K, px, px == 1 ? c->kb1_slots[K] : c->roll_slots[K][0][2],
+                                  c->roll_seg, std::min(lh, c->batch_seg_min), sel.n);
+  if (batch_partials_fit(c, sp.waves, "waves") < 0) return -1;
+  BatchRoll br{};
+  br.ra.b = bl.bufs;
+  br.ra.it = bl.it;
+  br.ra.bands = sp.bands;
+  br.ra.seg_rows = sp.seg_rows;
+  br.ra.waves = sp.waves;
+  set_batch_upc(c, br);
+  br.ps = bl.ps;
+  br.partials = c->bpartials;
+  br.nblk = c->bnblk;
+  br.sel = sel;
+  const dim3 grid((br.ra.waves + 3) / 4, sel.n);
+  const size_t tkp = prof_begin(c, st);
+#define KB_ROLL_M(FM)                                                                       \
+  if (px == 1)                                                                            \
+    hipLaunchKernelGGL((kb_iterate_roll<KK, 1, FM>), grid, dim3(256), 0, st, br);         \
+  else                                                                                    \
+    hipLaunchKernelGGL((kb_iterate_roll<KK, 2, FM>), grid, dim3(256), 0, st, br);
+#define KB_ROLL(K_)                 \
+  {                                 \
+    constexpr int KK = K_;          \
+    MATH_SWITCH(math, KB_ROLL_M)    \
+  }
+  switch (K) {
+    case 1: KB_ROLL(1) break;
+    case 2: KB_ROLL(2) break;
+    case 3: KB_ROLL(3) break;
+    default: KB_ROLL(4) break;
+  }
+#undef KB_ROLL
+#undef KB_ROLL_M
+  if (tkp) {   // k_iterate_roll's accounting (64*PX-px bands) per pair of the launch
+    const double Nl = (double)lw * lh;
+    int nz = 0;
+    for (int j = 0; j < sel.n; ++j) nz += sel.pzero.test(sel.idx[j]) ? 1 : 0;
+    prof_end(c, st, tkp, 0, (double)sel.n * Nl * 64.0 * K, batch_roll_hbm(sp, lh, K, px, Nl, sel.n, nz));
+  }
+  return sp.waves;
+}
+
+// every pair's flow of level s (its current u set) zoomed to level s-1 (the other set)
+static void batch_upsample(const BatchLevel &bl, BatchSel sel) {
+  tvl1_ctx *c = bl.c;
+  const Geometry &g = c->geo;
+  BatchUp up{};
+  set_batch_u(c, up);
+  up.ps = bl.ps;
+  up.sw = bl.lw;
+  up.sh = bl.lh;
+  up.sp = bl.P;
+  up.dw = g.ws[bl.s - 1];
+  up.dh = g.hs[bl.s - 1];
+  up.dp = g.ps[bl.s - 1];
+  up.fx = (float)(1.0 / ((double)up.dw / bl.lw));
+  up.fy = (float)(1.0 / ((double)up.dh / bl.lh));
+  up.mul = (float)(1.0 / c->prm.scale_step);
+  up.sel = sel;
+  if (contracts(bl.math))
+    hipLaunchKernelGGL(kb_upsample<true>, grid2(up.dw, up.dh, 2 * bl.n), kBlk2, 0, bl.st, up);
+  else
+    hipLaunchKernelGGL(kb_upsample<false>, grid2(up.dw, up.dh, 2 * bl.n), kBlk2, 0, bl.st, up);
+}
+
+static void batch_output(tvl1_ctx *c, int n, int W, int H, float *u, float *v, size_t fpitch,
+                         size_t fstride, BatchSel sel, hipStream_t st) {
+  BatchOut bo{};
+  set_batch_u(c, bo);
+  bo.ps = c->bps;
+  bo.W = W;
+  bo.H = H;
+  bo.P = c->geo.ps[0];
+  bo.u = u;
+  bo.v = v;
+  bo.fpitch = fpitch;
+  bo.fstride = fstride;
+  bo.sel = sel;
+  hipLaunchKernelGGL(kb_output, grid2(W, H, n), kBlk2, 0, st, bo);
+}
+
 static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size_t pitch0,
                                      size_t stride0, const uint8_t *I1, size_t pitch1,
                                      size_t stride1, const Seed *seed, int W, int H, float *u,
@@ -1649,10 +1894,7 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
   const tvl1_params &prm = c->prm;
   const Geometry &g = c->geo;
   const int L = g.L;
-  {
-    const tvl1_status r = ensure_batch(c, W, H, n, st);
-    if (r != TVL1_OK) return r;
-  }
+  TVL1_TRY(ensure_batch(c, W, H, n, st));
   const size_t ps = c->bps;
   // counted as a solve in progress (single-pair solves speculate and size their launches
   // by this count); the batched launches themselves are sized for every resident slot (the
@@ -1667,160 +1909,64 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
     c->marks.clear();
   }
 
-  // [A.1] convertTo + [A.2] pyramid
-  hipLaunchKernelGGL(kb_convert, grid2(W, H, 2 * n), kBlk2, 0, st, I0, pitch0, stride0, I1,
-                     pitch1, stride1, c->bI0s[0], c->bI1s[0], W, H, g.ps[0], c->bips[0]);
-  const float fdown = (float)(1.0 / prm.scale_step);
-  const int math = math_of(prm);
-  for (int s = 1; s < L; ++s) {
-#define KB_DOWN(C)                                                                             \
-  hipLaunchKernelGGL(kb_resize_down2<C>, grid2(g.ws[s], g.hs[s], 2 * n), kBlk2, 0, st,         \
-                     c->bI0s[s - 1], c->bI1s[s - 1], g.ws[s - 1], g.hs[s - 1], g.ps[s - 1],    \
-                     c->bips[s - 1], c->bI0s[s], c->bI1s[s], g.ws[s], g.hs[s], g.ps[s],       \
-                     c->bips[s], fdown, fdown);
-    if (contracts(math)) {
-      KB_DOWN(true)
-    } else {
-      KB_DOWN(false)
-    }
-#undef KB_DOWN
-  }
-  if (!seed) {   // u = 0 at the coarsest level, set 0 of every pair
-    for (int k = 0; k < 2; ++k)
-      HIP_TRY(c, hipMemsetAsync(c->bU[0][k], 0, ps * n * sizeof(float), st));
-  } else {
-    // [A.2b] every pair's seed pyramid (solve()'s chain): the first step reads the caller's
-    // planes, the steps alternate between the u sets and the last one writes set 0
-    const float fmul = (float)prm.scale_step;
-    const size_t tkf = prof_begin(c, st);
-    double fb = 0.0;
-    if (L == 1) {
-      hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2 * n), kBlk2, 0, st, seed->u0, seed->v0,
-                         (int)seed->pitch, seed->stride, c->bU[0][0], c->bU[0][1], W, H, g.ps[0], ps);
-      fb = (double)n * W * H * 16.0;
-    }
-    int set = L & 1;   // L - 1 steps end in set 0
-    for (int s = 1; s < L; ++s, set ^= 1) {
-      const float *s1 = s == 1 ? seed->u0 : c->bU[set ^ 1][0], *s2 = s == 1 ? seed->v0 : c->bU[set ^ 1][1];
-      const int sp = s == 1 ? (int)seed->pitch : g.ps[s - 1];
-      const size_t sps = s == 1 ? seed->stride : ps;
-#define KB_FLOW(C)                                                                             \
-  hipLaunchKernelGGL(kb_flow_down<C>, grid2(g.ws[s], g.hs[s], 2 * n), kBlk2, 0, st, s1, s2,    \
-                     g.ws[s - 1], g.hs[s - 1], sp, sps, c->bU[set][0], c->bU[set][1], g.ws[s], \
-                     g.hs[s], g.ps[s], ps, fdown, fdown, fmul);
-      if (contracts(math)) {
-        KB_FLOW(true)
-      } else {
-        KB_FLOW(false)
-      }
-#undef KB_FLOW
-      fb += (double)n * ((double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8);
-    }
-    prof_end(c, st, tkf, 2, fb);
-  }
+  batch_pyramid(c, n, I0, pitch0, stride0, I1, pitch1, stride1, W, H, st);
+  TVL1_TRY(batch_initial_flow(c, n, seed, W, H, st));
   HIP_TRY(c, hipGetLastError());
 
-  const float l_t = (float)(prm.lambda * prm.theta);
-  const float taut = (float)(prm.tau / prm.theta);
-  const float upmul = (float)(1.0 / prm.scale_step);
   BatchMask ubit{}, pbit{};
   std::vector<int64_t> level_iters((size_t)n * TVL1_MAX_LEVELS, 0), checks(n, 0), regathers(n, 0);
-  std::vector<int> nit(n);
-  std::vector<double> err(n), prev(n);
-  std::vector<char> act(n);
+  std::vector<int> nit(n), kb(n), hw;
+  std::vector<double> err(n), prev(n), prev_end(n);
+  std::vector<char> act(n), ends(n);
   // per pair: its previous warp on this level stopped at the first check, so this warp's
   // fused pass is predicted to stop there too and its constants are not stored (k_warp_iter's
   // store_c rule)
   std::vector<char> stopped_first(n, 0);
+  auto note_warp = [&](int b, int s, int wp, int iters) {   // a pair's iterations of a warp
+    level_iters[(size_t)b * TVL1_MAX_LEVELS + s] += iters;
+    if (stats && stats[b].warp_iterations && s * prm.warps + wp < stats[b].warp_iterations_capacity)
+      stats[b].warp_iterations[s * prm.warps + wp] = iters;
+  };
   for (int s = L - 1; s >= 0; --s) {
     const int lw = g.ws[s], lh = g.hs[s], P = g.ps[s];
     const double scaledEps = prm.epsilon * prm.epsilon * (double)lw * (double)lh;
     BatchMask pzero{};   // p = 0 at every level start
     for (int b = 0; b < n; ++b) pzero.set(b);
-    // RollBufs geometry of the batch arena (the kernels point it at each pair's planes)
-    RollBufs batch_bufs{};
+    BatchLevel bl{};
+    bl.c = c;
+    bl.st = st;
+    bl.n = n;
+    bl.s = s;
+    bl.lw = lw;
+    bl.lh = lh;
+    bl.P = P;
+    bl.math = math_of(prm);
+    bl.ps = ps;
     {
       const size_t bstride = (size_t)(c->bC[1] - c->bC[0]) * sizeof(float);
       const size_t lvl = (size_t)P * lh * sizeof(float);
-      batch_bufs.pstride = (unsigned)bstride;
-      batch_bufs.cb = (unsigned)(2 * bstride + lvl);
-      batch_bufs.ub = (unsigned)(bstride + lvl);
-      batch_bufs.pb = (unsigned)(3 * bstride + lvl);
+      bl.bufs.pstride = (unsigned)bstride;
+      bl.bufs.cb = (unsigned)(2 * bstride + lvl);
+      bl.bufs.ub = (unsigned)(bstride + lvl);
+      bl.bufs.pb = (unsigned)(3 * bstride + lvl);
     }
-    IterArgs it{};   // pass geometry and scalars (plane pointers are set per pair)
-    it.W = lw;
-    it.H = lh;
-    it.P = P;
-    it.l_t = l_t;
-    it.theta = (float)prm.theta;
-    it.gamma = 0.0f;
-    it.taut = taut;
-    it.taut_small = taut_small(taut);
-    // The coarsest level on chip (kb_small_level, one workgroup per pair: every warp's gather,
-    // iterations, residuals and stopping rule without leaving the workgroup) when it fits one
-    // workgroup's registers and LDS; u enters as 0 (or, seeded, as set 0's planes: <FM, true>)
-    // and leaves in set 0, and p is reset at every level anyway
+    bl.it = iter_args(prm, lw, lh, P, nullptr);   // (each pair's partials are set on the device)
+    bl.it.gamma = 0.0f;                           // the batched kernels are the gamma = 0 ones
+    // the coarsest level runs on chip when it fits one workgroup's registers and LDS (p is
+    // reset at every level anyway)
     const bool small = c->batch_small && s == L - 1 && prm.median_filtering <= 1 &&
                        lw <= 64 * kSmallWaves && lh <= kSmallR && lw * lh <= kSmallPx;
     if (small) {
-      const size_t need = (size_t)n * (prm.warps + 1) * sizeof(int);
-      if (need > c->small_bytes) {
-        const tvl1_status r = arena_alloc(c, &c->small_scratch, &c->small_bytes,
-                                          std::max<size_t>(need, 64 << 10), st);
-        if (r != TVL1_OK) return r;
-      }
-      BatchSmall sm{};
-      sm.I0 = c->bI0s[s];
-      sm.I1 = c->bI1s[s];
-      sm.u1 = c->bU[0][0];
-      sm.u2 = c->bU[0][1];
-      sm.ips = c->bips[s];
-      sm.ps = ps;
-      sm.W = lw;
-      sm.H = lh;
-      sm.P = P;
-      sm.warps = prm.warps;
-      sm.iterations = prm.iterations;
-      sm.eps_pos = prm.epsilon > 0;
-      sm.thr = scaledEps;
-      sm.it = it;
-      sm.warp_iters = reinterpret_cast<int *>(c->small_scratch);
-      sm.checks = sm.warp_iters + (size_t)n * prm.warps;
-      sm.sel = all;
-      const size_t tks = prof_begin(c, st);
-#define KB_SMALL(FM)                                                                               \
-  if (seed)                                                                                       \
-    hipLaunchKernelGGL((kb_small_level<FM, true>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm); \
-  else                                                                                            \
-    hipLaunchKernelGGL((kb_small_level<FM>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm);
-      MATH_SWITCH(math, KB_SMALL)
-#undef KB_SMALL
-      HIP_TRY(c, hipGetLastError());
-      std::vector<int> hw((size_t)n * (prm.warps + 1));
-      HIP_TRY(c, hipMemcpyAsync(hw.data(), c->small_scratch, need, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      int64_t it_sum = 0;
+      TVL1_TRY(batch_small_level(bl, all, seed != nullptr, scaledEps, hw));
       for (int b = 0; b < n; ++b) {
-        for (int wp = 0; wp < prm.warps; ++wp) {
-          const int nb = hw[(size_t)b * prm.warps + wp];
-          level_iters[(size_t)b * TVL1_MAX_LEVELS + s] += nb;
-          it_sum += nb;
-          if (stats && stats[b].warp_iterations &&
-              s * prm.warps + wp < stats[b].warp_iterations_capacity)
-            stats[b].warp_iterations[s * prm.warps + wp] = nb;
-        }
+        for (int wp = 0; wp < prm.warps; ++wp) note_warp(b, s, wp, hw[(size_t)b * prm.warps + wp]);
         checks[b] += hw[(size_t)n * prm.warps + b];
       }
-      // its own class (3): SURVEY 8(d)'s bytes of every iteration and warp it ran, but from HBM
-      // it only reads I0, I1 and writes u once, so it would skew class 0's HBM roofline
-      prof_end(c, st, tks, 3, (double)lw * lh * (64.0 * it_sum + 40.0 * n * prm.warps),
-               (double)lw * lh * 16.0 * n);
     }
     for (int wp = 0; wp < (small ? 0 : prm.warps); ++wp) {
       if (prm.median_filtering > 1) {   // build-only median of u before each warp
         BatchMedian md{};
-        for (int k = 0; k < 2; ++k)
-          for (int j = 0; j < 2; ++j) md.U[k][j] = c->bU[k][j];
+        set_batch_u(c, md);
         md.ps = ps;
         md.W = lw;
         md.H = lh;
@@ -1831,89 +1977,29 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
         hipLaunchKernelGGL(kb_median, grid2(lw, lh, 2 * n), kBlk2, 0, st, md);
         for (int b = 0; b < n; ++b) ubit.flip(b);
       }
+      BatchSel cur = all;   // every pair, with its current buffer sets
+      cur.ubit = ubit;
       // warpBackward fused with the warp's first pass, which is 2 iterations ending in the
       // first check for every pair (procOneScale with epsilon > 0, iterations >= 2)
       const bool fuse = c->batch_fuse && prm.epsilon > 0 && prm.iterations >= 2;
+      // a pair stores its constants unless its previous warp stopped at the first check
+      auto stores = [&](int b) { return wp == 0 || !stopped_first[b] || !c->batch_store_pred; };
       if (fuse) {
-        BatchWI wi{};
-        wi.w.ra.b = batch_bufs;
-        wi.w.ra.it = it;
-        wi.w.ra.bands = (lw + 123) / 124;
-        wi.w.ra.seg_rows = roll_segment(wi.w.ra.bands * n, lh, 2 + 6, c->witer_slots);
-        wi.w.ra.waves = wi.w.ra.bands * ((lh + wi.w.ra.seg_rows - 1) / wi.w.ra.seg_rows);
-        if (wi.w.ra.waves > c->bnblk)
-          return set_err(c, TVL1_EHIP, "internal: %d blocks > batch partials %d", wi.w.ra.waves, c->bnblk);
-        wi.I0 = c->bI0s[s];
-        wi.I1 = c->bI1s[s];
-        for (int k = 0; k < 2; ++k)
-          for (int j = 0; j < 2; ++j) wi.U[k][j] = c->bU[k][j];
-        for (int k = 0; k < 2; ++k)
-          for (int j = 0; j < 4; ++j) wi.Pp[k][j] = c->bP[k][j];
-        for (int j = 0; j < 3; ++j) wi.C[j] = c->bC[j];
-        wi.ips = c->bips[s];
-        wi.ps = ps;
-        wi.partials = c->bpartials;
-        wi.nblk = wi.w.ra.waves;
-        wi.sel = all;
-        wi.sel.ubit = ubit;
-        wi.sel.pbit = pbit;
-        wi.sel.pzero = pzero;
+        cur.pbit = pbit;
+        cur.pzero = pzero;
         int nstore = 0;
         for (int b = 0; b < n; ++b)
-          if (wp == 0 || !stopped_first[b] || !c->batch_store_pred) {
-            wi.sel.storec.set(b);
+          if (stores(b)) {
+            cur.storec.set(b);
             ++nstore;
           }
-        const size_t tkw = prof_begin(c, st);
-#define KB_WITER(FM)                                                                             \
-  if (c->wi_nc == 2)                                                                            \
-    hipLaunchKernelGGL((kb_warp_iter<6, FM, 2>), dim3(wi.w.ra.waves, n), dim3(256), 0, st, wi); \
-  else                                                                                          \
-    hipLaunchKernelGGL((kb_warp_iter<6, FM, 1>), dim3(wi.w.ra.waves, n), dim3(192), 0, st, wi);
-        MATH_SWITCH(math, KB_WITER)
-#undef KB_WITER
-        if (tkw) {   // k_warp_iter's accounting per pair (constants always stored), x n
-          const int seg = wi.w.ra.seg_rows, segs = (lh + seg - 1) / seg;
-          double rows = 0.0;
-          for (int sg = 0; sg < segs; ++sg) {
-            const int ys = sg * seg, ye = std::min(ys + seg, lh);
-            rows += std::min(ye - 1 + 2, lh - 1) - std::max(ys - 2, 0) + 1;
-          }
-          const double Nl = (double)lw * lh;
-          int nz = 0;   // pairs whose p is zero (a level's first warp): p not loaded
-          for (int b = 0; b < n; ++b) nz += pzero.test(b) ? 1 : 0;
-          const double band_bytes = (double)wi.w.ra.bands * 128 * rows * 4.0;
-          const double hbm = band_bytes * ((double)nz * 3 + (double)(n - nz) * 7 +
-                                           (double)n * wi_ww<6, 128>() / 128) +
-                             Nl * 4.0 * (6.0 * n + 3.0 * nstore);
-          prof_end(c, st, tkw, 0, (double)n * Nl * (64.0 * 2 + 40.0), hbm);
-        }
-        hipLaunchKernelGGL(kb_reduce, dim3(n), dim3(kBlock), 0, st, c->bpartials,
-                           (size_t)wi.w.ra.waves, wi.w.ra.waves, all, c->pinned_dev + 8);
+        const int waves = launch_batch_warp_iter(bl, cur, nstore);
+        if (waves < 0) return TVL1_EHIP;
+        hipLaunchKernelGGL(kb_reduce, dim3(n), dim3(kBlock), 0, st, c->bpartials, (size_t)waves, waves,
+                           all, c->pinned_dev + 8);
         HIP_TRY(c, hipEventRecord(c->ev_check[0], st));
-      } else {   // k_warp_ring's streaming LDS-ring gather, per pair
-        BatchRing br{};
-        br.wa.W = lw;
-        br.wa.H = lh;
-        br.wa.P = P;
-        br.wa.bands = (lw + 63) / 64;
-        br.wa.seg_rows = roll_segment(br.wa.bands * n, lh, 6, c->warp_ring_slots);
-        br.wa.waves = br.wa.bands * ((lh + br.wa.seg_rows - 1) / br.wa.seg_rows);
-        br.I0 = c->bI0s[s];
-        br.I1 = c->bI1s[s];
-        for (int k = 0; k < 2; ++k)
-          for (int j = 0; j < 2; ++j) br.U[k][j] = c->bU[k][j];
-        for (int j = 0; j < 3; ++j) br.C[j] = c->bC[j];
-        br.ips = c->bips[s];
-        br.ps = ps;
-        br.sel = all;
-        br.sel.ubit = ubit;
-        const size_t tkr = prof_begin(c, st);
-#define KB_RING(FM) \
-  hipLaunchKernelGGL((kb_warp_ring<6, 2, FM>), dim3(br.wa.waves, n), dim3(128), 0, st, br);
-        MATH_SWITCH(math, KB_RING)
-#undef KB_RING
-        prof_end(c, st, tkr, 1, (double)n * lw * lh * 40.0, (double)n * lw * lh * 28.0);
+      } else {
+        launch_batch_ring(bl, cur);
       }
       int nact = 0;
       for (int b = 0; b < n; ++b) {
@@ -1929,7 +2015,7 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
         BatchSel regather{};   // pairs that continue without stored constants
         regather.ubit = ubit;  // u^0: the set the fused pass read
         for (int b = 0; b < n; ++b) {
-          const bool stored = wp == 0 || !stopped_first[b] || !c->batch_store_pred;
+          const bool stored = stores(b);
           nit[b] = 2;
           ubit.flip(b);
           pbit.flip(b);
@@ -1943,65 +2029,38 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
           if (act[b] && !stored) regather.idx[regather.n++] = (uint8_t)b;
         }
         if (regather.n > 0) {   // a wrong guess: gather the constants (k_warp_ring's body)
-          BatchRing br{};
-          br.wa.W = lw;
-          br.wa.H = lh;
-          br.wa.P = P;
-          br.wa.bands = (lw + 63) / 64;
-          br.wa.seg_rows = roll_segment(br.wa.bands * regather.n, lh, 6, c->warp_ring_slots);
-          br.wa.waves = br.wa.bands * ((lh + br.wa.seg_rows - 1) / br.wa.seg_rows);
-          br.I0 = c->bI0s[s];
-          br.I1 = c->bI1s[s];
-          for (int k = 0; k < 2; ++k)
-            for (int j = 0; j < 2; ++j) br.U[k][j] = c->bU[k][j];
-          for (int j = 0; j < 3; ++j) br.C[j] = c->bC[j];
-          br.ips = c->bips[s];
-          br.ps = ps;
-          br.sel = regather;
-          const size_t tkr = prof_begin(c, st);
-#define KB_RING(FM) \
-  hipLaunchKernelGGL((kb_warp_ring<6, 2, FM>), dim3(br.wa.waves, regather.n), dim3(128), 0, st, br);
-          MATH_SWITCH(math, KB_RING)
-#undef KB_RING
-          prof_end(c, st, tkr, 1, (double)regather.n * lw * lh * 40.0,
-                   (double)regather.n * lw * lh * 28.0);
+          launch_batch_ring(bl, regather);
           for (int j = 0; j < regather.n; ++j) ++regathers[regather.idx[j]];
         }
       } else {
         for (int b = 0; b < n; ++b) stopped_first[b] = 0;
       }
       while (nact > 0) {
-        // each active pair's pass (the single-pair rule): k iterations up to and including
-        // its next check, at most kTbMax
-        std::vector<int> kb(n, 0);
-        std::vector<char> ends(n, 0);
+        // each active pair's pass (the single-pair rule, sched_after): k iterations up to and
+        // including its next check, at most kTbMax
         int kmin = kTbMax;
         for (int b = 0; b < n; ++b) {
+          kb[b] = 0;
+          ends[b] = 0;
           if (!act[b]) continue;
-          int k = 0;
-          double ps_ = prev[b];
-          while (k < kTbMax && nit[b] + k < prm.iterations) {
-            const bool ce = (prm.epsilon > 0) && ((nit[b] + k) & 1) && (ps_ < scaledEps);
-            ++k;
-            if (ce) {
-              ends[b] = 1;
-              break;
-            }
-            ps_ -= scaledEps;
-          }
-          kb[b] = k;
-          kmin = std::min(kmin, k);
+          bool ce = false;
+          kb[b] = sched_after(prev[b], scaledEps, nit[b], prm.iterations, kTbMax, prm.epsilon > 0, &ce,
+                              &prev_end[b]);
+          ends[b] = ce;
+          kmin = std::min(kmin, kb[b]);
         }
         // r4: pairs grouped by their pass length, one launch per group, so every pair runs
         // its whole pass.  TVL1_BATCH_GROUP=0 keeps r3's lock step: one launch of
-        // the shortest pass any active pair allows, the others split theirs.
+        // the shortest pass any active pair allows, the others split theirs (their schedule
+        // clipped to kmin iterations: no check).
         if (!c->batch_group)
           for (int b = 0; b < n; ++b)
             if (act[b] && kb[b] > kmin) {
-              kb[b] = kmin;
-              ends[b] = 0;
+              bool ce = false;
+              kb[b] = sched_after(prev[b], scaledEps, nit[b], prm.iterations, kmin, prm.epsilon > 0, &ce,
+                                  &prev_end[b]);
+              ends[b] = ce;
             }
-        int ngroups = 0;
         for (int K = 1; K <= kTbMax; ++K) {
           BatchSel sel{};
           BatchSel chk{};
@@ -2014,91 +2073,20 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
             }
           }
           if (sel.n == 0) continue;
-          ++ngroups;
           sel.ubit = ubit;
           sel.pbit = pbit;
           sel.pzero = pzero;
-          int blocks;   // residual partials per pair (pair stride c->bnblk)
-          {   // wavefront pipelines: 64*PX-px bands down the whole level, one per wave
-            BatchRoll br{};
-            br.ra.b = batch_bufs;
-            br.ra.it = it;
-            // PX = 1 (64-px bands) on narrow levels when TVL1_BATCH_PX1_W asks for it
-            const int px = lw <= c->batch_px1_w ? 1 : 2;
-            const int halo = px == 1 ? K : (K + 1) / 2 * 2;   // roll_halo<K, PX>
-            br.ra.bands = (lw + 64 * px - 2 * halo - 1) / (64 * px - 2 * halo);
-            // segments sized so the launch's wavefronts fill whole rounds of resident slots,
-            // but never shorter than min(rows, batch_seg_min): a pass group of a few pairs (or
-            // a tiny level) would otherwise be cut into short segments that repeat the 2K-row
-            // halo to fill slots the other batch in flight fills anyway (r5: one segment per
-            // band on the strips' <= 100-row levels, +1.7 % strip solves/s,
-            // profiles/r5/ab/strips_seg/)
-            br.ra.seg_rows = c->roll_seg > 0 ? std::max(c->roll_seg, kRollMinSeg)
-                                             : std::max(roll_segment(br.ra.bands * sel.n, lh, K,
-                                                                     px == 1 ? c->kb1_slots[K]
-                                                                             : c->roll_slots[K][0][2]),
-                                                        std::min(lh, c->batch_seg_min));
-            br.ra.waves = br.ra.bands * ((lh + br.ra.seg_rows - 1) / br.ra.seg_rows);
-            blocks = br.ra.waves;
-            if (blocks > c->bnblk)
-              return set_err(c, TVL1_EHIP, "internal: %d waves > batch partials %d", blocks, c->bnblk);
-            for (int k = 0; k < 2; ++k)
-              for (int j = 0; j < 2; ++j) br.U[k][j] = c->bU[k][j];
-            for (int k = 0; k < 2; ++k)
-              for (int j = 0; j < 4; ++j) br.Pp[k][j] = c->bP[k][j];
-            for (int j = 0; j < 3; ++j) br.C[j] = c->bC[j];
-            br.ps = ps;
-            br.partials = c->bpartials;
-            br.nblk = c->bnblk;
-            br.sel = sel;
-            const dim3 grid((br.ra.waves + 3) / 4, sel.n);
-            const size_t tkp = prof_begin(c, st);
-#define KB_ROLL_M(FM)                                                                       \
-  if (px == 1)                                                                            \
-    hipLaunchKernelGGL((kb_iterate_roll<KK, 1, FM>), grid, dim3(256), 0, st, br);         \
-  else                                                                                    \
-    hipLaunchKernelGGL((kb_iterate_roll<KK, 2, FM>), grid, dim3(256), 0, st, br);
-#define KB_ROLL(K_)                 \
-  {                                 \
-    constexpr int KK = K_;          \
-    MATH_SWITCH(math, KB_ROLL_M)    \
-  }
-            switch (K) {
-              case 1: KB_ROLL(1) break;
-              case 2: KB_ROLL(2) break;
-              case 3: KB_ROLL(3) break;
-              default: KB_ROLL(4) break;
-            }
-#undef KB_ROLL
-#undef KB_ROLL_M
-            if (tkp) {   // k_iterate_roll's accounting (64*PX-px bands) per pair of the launch
-              const int seg = br.ra.seg_rows, segs = (lh + seg - 1) / seg;
-              double rows = 0.0;
-              for (int sg = 0; sg < segs; ++sg) {
-                const int ys = sg * seg, ye = std::min(ys + seg, lh);
-                rows += std::min(ye - 1 + K, lh - 1) - std::max(ys - K, 0) + 1;
-              }
-              const double Nl = (double)lw * lh;
-              int nz = 0;
-              for (int j = 0; j < sel.n; ++j) nz += pzero.test(sel.idx[j]) ? 1 : 0;
-              const double band_bytes = (double)br.ra.bands * 64 * px * rows * 4.0;
-              const double hbm = band_bytes * ((double)sel.n * 5 + (double)(sel.n - nz) * 4) +
-                                 (double)sel.n * Nl * 4.0 * 6.0;
-              prof_end(c, st, tkp, 0, (double)sel.n * Nl * 64.0 * K, hbm);
-            }
-          }
+          const int blocks = launch_batch_roll(bl, K, sel);
+          if (blocks < 0) return TVL1_EHIP;
           if (chk.n > 0)
             hipLaunchKernelGGL(kb_reduce, dim3(chk.n), dim3(kBlock), 0, st, c->bpartials,
                                (size_t)c->bnblk, blocks, chk, c->pinned_dev + 8);
         }
-        (void)ngroups;
         bool any_check = false;
         for (int b = 0; b < n; ++b) {
           if (!act[b]) continue;
-          const int K = kb[b];
-          for (int i = 0; i < K; ++i)
-            if (!(ends[b] && i == K - 1)) prev[b] -= scaledEps;
-          nit[b] += K;
+          prev[b] = prev_end[b];
+          nit[b] += kb[b];
           ubit.flip(b);
           pbit.flip(b);
           pzero.clear(b);
@@ -2122,99 +2110,29 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
           nact += act[b];
         }
       }
-      for (int b = 0; b < n; ++b) {
-        level_iters[(size_t)b * TVL1_MAX_LEVELS + s] += nit[b];
-        if (stats && stats[b].warp_iterations &&
-            s * prm.warps + wp < stats[b].warp_iterations_capacity)
-          stats[b].warp_iterations[s * prm.warps + wp] = nit[b];
-      }
+      for (int b = 0; b < n; ++b) note_warp(b, s, wp, nit[b]);
     }
     HIP_TRY(c, hipGetLastError());
     if (s == 0) break;
-    BatchUp up{};
-    for (int k = 0; k < 2; ++k)
-      for (int j = 0; j < 2; ++j) up.U[k][j] = c->bU[k][j];
-    up.ps = ps;
-    up.sw = lw;
-    up.sh = lh;
-    up.sp = P;
-    up.dw = g.ws[s - 1];
-    up.dh = g.hs[s - 1];
-    up.dp = g.ps[s - 1];
-    up.fx = (float)(1.0 / ((double)up.dw / lw));
-    up.fy = (float)(1.0 / ((double)up.dh / lh));
-    up.mul = upmul;
-    up.sel = all;
-    up.sel.ubit = ubit;
-    if (contracts(math))
-      hipLaunchKernelGGL(kb_upsample<true>, grid2(up.dw, up.dh, 2 * n), kBlk2, 0, st, up);
-    else
-      hipLaunchKernelGGL(kb_upsample<false>, grid2(up.dw, up.dh, 2 * n), kBlk2, 0, st, up);
+    BatchSel cur = all;
+    cur.ubit = ubit;
+    batch_upsample(bl, cur);
     for (int b = 0; b < n; ++b) ubit.flip(b);
   }
-  BatchOut bo{};
-  for (int k = 0; k < 2; ++k)
-    for (int j = 0; j < 2; ++j) bo.U[k][j] = c->bU[k][j];
-  bo.ps = ps;
-  bo.W = W;
-  bo.H = H;
-  bo.P = g.ps[0];
-  bo.u = u;
-  bo.v = v;
-  bo.fpitch = fpitch;
-  bo.fstride = fstride;
-  bo.sel = all;
-  bo.sel.ubit = ubit;
-  hipLaunchKernelGGL(kb_output, grid2(W, H, n), kBlk2, 0, st, bo);
+  BatchSel cur = all;
+  cur.ubit = ubit;
+  batch_output(c, n, W, H, u, v, fpitch, fstride, cur, st);
   HIP_TRY(c, hipGetLastError());
-  if (stats) {
-    for (int b = 0; b < n; ++b) {
-      tvl1_stats &sb = stats[b];
-      sb.levels = L;
-      int64_t tot = 0;
-      int64_t li[TVL1_MAX_LEVELS] = {};
-      for (int s = 0; s < TVL1_MAX_LEVELS; ++s) {
-        li[s] = s < L ? level_iters[(size_t)b * TVL1_MAX_LEVELS + s] : 0;
-        sb.level_width[s] = s < L ? g.ws[s] : 0;
-        sb.level_height[s] = s < L ? g.hs[s] : 0;
-        sb.level_iterations[s] = li[s];
-        tot += li[s];
-      }
-      sb.iterations_total = tot;
-      sb.checks_total = checks[b];
-      sb.speculation_misses = regathers[b];   // constants not stored, then needed (re-gathered)
-      sb.algorithmic_bytes = survey_bytes(g, prm.warps, li);
-      for (int k = 0; k < 4; ++k) {
-        sb.kernel_ms[k] = 0.0;
-        sb.kernel_launches[k] = 0;
-        sb.kernel_bytes[k] = 0.0;
-        sb.kernel_hbm_bytes[k] = 0.0;
-      }
-    }
-  }
+  if (stats)
+    for (int b = 0; b < n; ++b)   // misses: constants not stored, then needed (re-gathered)
+      fill_stats(&stats[b], g, prm.warps, &level_iters[(size_t)b * TVL1_MAX_LEVELS], checks[b],
+                 (int32_t)regathers[b]);
   // with tvl1_set_profiling: every pair of the chunk reports the chunk's launches (each
   // launch serves all its pairs; bytes are summed over them)
-  if (c->profiling && !c->marks.empty()) {
-    HIP_TRY(c, hipEventSynchronize(c->ev_pool[c->marks.back().b]));
-    double ms[4] = {}, by[4] = {}, hb[4] = {};
-    int64_t nl[4] = {};
-    for (const auto &m : c->marks) {
-      float t = 0.f;
-      HIP_TRY(c, hipEventElapsedTime(&t, c->ev_pool[m.a], c->ev_pool[m.b]));
-      ms[m.cls] += t;
-      nl[m.cls] += 1;
-      by[m.cls] += m.bytes;
-      hb[m.cls] += m.hbm_bytes;
-    }
-    if (stats)
-      for (int b = 0; b < n; ++b)
-        for (int k = 0; k < 4; ++k) {
-          stats[b].kernel_ms[k] = ms[k];
-          stats[b].kernel_launches[k] = nl[k];
-          stats[b].kernel_bytes[k] = by[k];
-          stats[b].kernel_hbm_bytes[k] = hb[k];
-        }
-  }
+  ClassTotals tot;
+  TVL1_TRY(sum_marks(c, tot));
+  if (stats && c->profiling && !c->marks.empty())
+    for (int b = 0; b < n; ++b) put_class_totals(&stats[b], tot);
   return TVL1_OK;
 }
 

@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tvl1_plan.hpp"   // constants shared with the host plan, sched_after
+
 // The non-template kernels are defined once, in tvl1_engine.hip's translation unit.
 // tvl1_passes.hip includes these headers for its template instantiations only: there they
 // are declared as never-instantiated templates, so that unit emits no code for them.
@@ -40,9 +42,7 @@
 
 namespace tvl1k {
 
-constexpr int kWave = 64;
-constexpr int kBlock = 256;                 // 4 waves
-constexpr int kSegPx = (kWave - 2) * 4;     // 248 useful px per wave (lanes 1..62)
+constexpr int kBlock = 256;                 // 4 waves (kWave, kSegPx: tvl1_plan.hpp)
 constexpr float kFltEps = 1.1920928955078125e-07f;  // numeric_limits<float>::epsilon()
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
@@ -1559,8 +1559,7 @@ __global__ __launch_bounds__((64 / PX) * RH / NG, PX == 2 ? 8 : 1) void k_iterat
 // thread, 64 x 64 regions, needs 165 VGPRs -- one block per CU -- and was 49 % slower.)  Same
 // estimate_u / dual_component arithmetic, so the same bits (the region-edge rows take their
 // own row as the neighbour, as k_iterate_tb's LDS clamp does; no stored cell depends on them).
-constexpr int kTb4Groups = 16;   // row groups (threads per column) of a region (32: -6 %, r5)
-constexpr int kTb4RowsPerThread = 3;
+// (kTb4Groups row groups of kTb4RowsPerThread rows each: tvl1_plan.hpp)
 
 // The iterations of one k_iterate_tb4 region.  IN: the region lies inside the image with a
 // margin (x > 0, y > 0, x + 1 < W, y + 1 < H for every px), so the border forms are constant
@@ -1730,7 +1729,6 @@ __global__ __launch_bounds__(32 * kTb4Groups, 4) void k_iterate_tb4(TBArgs t) {
 // VALU-bound for K >= 3 (the halo is recomputed, so a small one matters) and HBM-bound for
 // K <= 2.  Arithmetic is estimate_u_px / dual_px, the same as the other iteration kernels
 // (bit-identical results).
-constexpr int kRollMax = 4;
 constexpr int kRollAhead = 2;   // input rows loaded ahead of the row entering the pipeline
 // rows loaded ahead by k_iterate_roll<.., PX>: 16-byte loads (PX = 4) keep as many bytes in
 // flight one row ahead as 8-byte loads two rows ahead, with one ring row less
@@ -2883,26 +2881,7 @@ struct CheckGate {
   int pk, pcalc;
 };
 
-// procOneScale's schedule from a residual: iterations up to and including the next check
-// (the host's copy is sched_after in tvl1_engine.hip; the same double operations)
-__host__ __device__ inline int sched_after(double prev, double thr, int n, int iters, int kmax,
-                                           int eps_pos, bool *calc_end, double *prev_end) {
-  int k = 0;
-  bool ce = false;
-  while (k < kmax && n + k < iters) {
-    const bool calc = eps_pos && ((n + k) & 1) && prev < thr;
-    ++k;
-    if (calc) {
-      ce = true;
-      break;
-    }
-    prev -= thr;
-  }
-  *calc_end = ce;
-  *prev_end = prev;
-  return k;
-}
-
+// (procOneScale's schedule from a residual: sched_after, tvl1_plan.hpp)
 TVL1_PLAIN __global__ void k_reduce(const double *__restrict__ partials, int n, double *__restrict__ out,
                          unsigned long long *seq_out, unsigned long long seq, CheckGate g) {
   if (gated_off(g.in, g.in_seq)) return;

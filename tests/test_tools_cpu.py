@@ -51,7 +51,7 @@ def test_tool_knobs_exist_in_engine():
 
 
 @pytest.mark.skipif(shutil.which("/opt/rocm/bin/hipcc") is None, reason="no hipcc")
-@pytest.mark.parametrize("probe", ["wi_probe.hip", "div_check.hip", "sqrt_check.hip"])
+@pytest.mark.parametrize("probe", ["wi_probe.hip", "wi_dyn.hip", "div_check.hip", "sqrt_check.hip"])
 def test_engine_probes_compile(probe, tmp_path):
     """The probes that include the engine's headers build against HEAD (device code
     only, syntax and semantics: no link, so no GPU needed)."""

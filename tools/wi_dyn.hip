@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "tvl1_plan.hpp"   // roll_segment: the engine's segment rule
 #include "tvl1_kernels.hpp"
 
 using namespace tvl1k;
@@ -65,23 +66,6 @@ __global__ __launch_bounds__(64 * NC + BW) void k_dyn(WarpIterArgs w, const Item
     ts[2 * blockIdx.x] = t0;
     ts[2 * blockIdx.x + 1] = t1;
   }
-}
-
-static int roll_segment(int bands, int lh, int k, int slots) {   // the engine's rule
-  int best = lh;
-  long best_cost = -1;
-  for (int R = 1; R <= 4; ++R) {
-    const int segs = std::max(1, R * slots / bands);
-    const int seg = std::max(8, (lh + segs - 1) / segs);
-    const long waves = (long)bands * ((lh + seg - 1) / seg);
-    const long rounds = (waves + slots - 1) / slots;
-    const long cost = rounds * (seg + 2 * k);
-    if (best_cost < 0 || cost < best_cost) {
-      best_cost = cost;
-      best = seg;
-    }
-  }
-  return best;
 }
 
 // per XCD x: rows [x H / 8, (x+1) H / 8) of every band; the first nblk items S1 rows (bands

@@ -16,6 +16,7 @@
 #ifdef WI_BARRIER   // -DWI_BARRIER: also time each wave's barrier waits (perturbs the timing)
 #define TVL1_BARRIER_PROBE
 #endif
+#include "tvl1_plan.hpp"   // roll_segment: the engine's segment rule
 #include "tvl1_kernels.hpp"
 
 using namespace tvl1k;
@@ -75,23 +76,6 @@ __global__ __launch_bounds__(64 * NC + BW) WI_ATTR void k_probe(WarpIterArgs w, 
     o[2] = hw;
     o[3] = xcc;
   }
-}
-
-static int roll_segment(int bands, int lh, int k, int slots) {
-  int best = lh;
-  long best_cost = -1;
-  for (int R = 1; R <= 4; ++R) {
-    const int segs = std::max(1, R * slots / bands);
-    const int seg = std::max(8, (lh + segs - 1) / segs);
-    const long waves = (long)bands * ((lh + seg - 1) / seg);
-    const long rounds = (waves + slots - 1) / slots;
-    const long cost = rounds * (seg + 2 * k);
-    if (best_cost < 0 || cost < best_cost) {
-      best_cost = cost;
-      best = seg;
-    }
-  }
-  return best;
 }
 
 int main(int argc, char **argv) {
