@@ -25,6 +25,7 @@
 #include "tvl1_kernels.hpp"
 #include "tvl1_batch.hpp"
 #include "tvl1_align.hpp"
+#include "tvl1_stack.hpp"
 
 // the iteration passes are compiled in tvl1_passes.hip (another instruction scheduler)
 namespace tvl1k {
@@ -188,6 +189,12 @@ struct tvl1_ctx {
     double hbm_bytes;  // compulsory bytes of this implementation
   };
   std::vector<Mark> marks;
+  // the same for the slice-list calls (tvl1_blend6_u8, tvl1_half_u8, tvl1_remap_flow_u8): they
+  // run outside a solve, so their marks wait here, with events of their own, for the next
+  // solve's totals (class 2)
+  std::vector<hipEvent_t> xev_pool;
+  size_t xev_used = 0;
+  std::vector<Mark> xmarks;
 };
 
 static size_t prof_begin(tvl1_ctx *c, hipStream_t st) {
@@ -569,6 +576,19 @@ struct ClassTotals {
   int64_t launches[4] = {};
 };
 static tvl1_status sum_marks(tvl1_ctx *c, ClassTotals &t) {
+  if (c->profiling && !c->xmarks.empty()) {   // slice-list calls since the last solve
+    for (const auto &m : c->xmarks) {
+      float ms = 0.f;
+      HIP_TRY(c, hipEventSynchronize(c->xev_pool[m.b]));
+      HIP_TRY(c, hipEventElapsedTime(&ms, c->xev_pool[m.a], c->xev_pool[m.b]));
+      t.ms[m.cls] += ms;
+      t.launches[m.cls] += 1;
+      t.bytes[m.cls] += m.bytes;
+      t.hbm[m.cls] += m.hbm_bytes;
+    }
+    c->xmarks.clear();
+    c->xev_used = 0;
+  }
   if (!c->profiling || c->marks.empty()) return TVL1_OK;
   HIP_TRY(c, hipEventSynchronize(c->ev_pool[c->marks.back().b]));
   for (const auto &m : c->marks) {
@@ -2923,6 +2943,112 @@ tvl1_status tvl1_postprocess_affine(tvl1_ctx *c, float *u, float *v, size_t fp, 
   return TVL1_OK;
 }
 
+// ---- Average-flow alignment of a slice list (added under ABI 9; kernels in tvl1_stack.hpp) ----
+// Profiling marks of these calls (class 2): kept apart from a solve's, which are reset when
+// the solve starts, and added to the next solve's totals (sum_marks).  At most kStackMarks
+// wait; a caller that never solves loses the later ones, not memory.
+static constexpr size_t kStackMarks = 1024;
+static size_t xprof_begin(tvl1_ctx *c, hipStream_t st) {
+  if (!c->profiling || c->xmarks.size() >= kStackMarks) return 0;
+  while (c->xev_used + 2 > c->xev_pool.size()) {
+    hipEvent_t e;
+    if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return 0;
+    c->xev_pool.push_back(e);
+  }
+  const size_t a = c->xev_used++;
+  (void)hipEventRecord(c->xev_pool[a], st);
+  return a + 1;
+}
+static void xprof_end(tvl1_ctx *c, hipStream_t st, size_t tok, double bytes) {
+  if (tok == 0) return;
+  const size_t b = c->xev_used++;
+  (void)hipEventRecord(c->xev_pool[b], st);
+  c->xmarks.push_back({2, tok - 1, b, bytes, bytes});
+}
+
+static inline dim3 grid_lanes(int w, int h, int px) {
+  return dim3(((w + px - 1) / px + 63) / 64, (h + 3) / 4, 1);
+}
+
+void tvl1_blend6_weights(float w[6]) {
+  if (!w) return;
+  const float k[6] = {kBlendW0, kBlendW1, kBlendW2, kBlendW2, kBlendW1, kBlendW0};
+  for (int i = 0; i < 6; ++i) w[i] = k[i];
+}
+
+tvl1_status tvl1_blend6_u8(tvl1_ctx *c, const uint8_t *const frames[6], const size_t pitches[6],
+                           int32_t W, int32_t H, uint8_t *dst, size_t dp, void *stream) {
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  if (!frames || !pitches || !dst) return set_err(c, TVL1_EINVAL, "null argument");
+  if (W <= 0 || H <= 0) return set_err(c, TVL1_ESIZE, "bad size %dx%d", W, H);
+  Blend6Args a;
+  for (int k = 0; k < 6; ++k) {
+    if (!frames[k]) return set_err(c, TVL1_EINVAL, "frame %d is NULL", k);
+    if (pitches[k] < (size_t)W) return set_err(c, TVL1_EINVAL, "pitch %d below the row size", k);
+    a.f[k] = frames[k];
+    a.pitch[k] = pitches[k];
+  }
+  if (dp < (size_t)W) return set_err(c, TVL1_EINVAL, "dst pitch below the row size");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t tok = xprof_begin(c, st);
+  hipLaunchKernelGGL(k_blend6_u8, grid_lanes(W, H, kStackPx), kBlk2, 0, st, a, W, H, dst, dp);
+  xprof_end(c, st, tok, 7.0 * W * H);
+  HIP_TRY(c, hipGetLastError());
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_half_u8(tvl1_ctx *c, const uint8_t *src, size_t sp, int32_t W, int32_t H,
+                         uint8_t *dst, size_t dp, void *stream) {
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  if (!src || !dst) return set_err(c, TVL1_EINVAL, "null argument");
+  if (W <= 0 || H <= 0) return set_err(c, TVL1_ESIZE, "bad size %dx%d", W, H);
+  if ((W | H) & 1) return set_err(c, TVL1_EINVAL, "tvl1_half_u8 takes even sizes (got %dx%d)", W, H);
+  if (sp < (size_t)W || dp < (size_t)(W / 2)) return set_err(c, TVL1_EINVAL, "pitch below the row size");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t tok = xprof_begin(c, st);
+  hipLaunchKernelGGL(k_half_u8, grid_lanes(W / 2, H / 2, kStackPx), kBlk2, 0, st, src, sp, W / 2,
+                     H / 2, dst, dp);
+  xprof_end(c, st, tok, 1.25 * W * H);
+  HIP_TRY(c, hipGetLastError());
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_remap_flow_u8(tvl1_ctx *c, const uint8_t *frame, size_t pitch, int32_t W, int32_t H,
+                               const float *u, const float *v, size_t fpitch, int32_t fw,
+                               int32_t fh, double gain, int32_t border, uint8_t *dst, size_t dp,
+                               void *stream) {
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  if (!frame || !u || !v || !dst) return set_err(c, TVL1_EINVAL, "null argument");
+  if (W <= 0 || H <= 0) return set_err(c, TVL1_ESIZE, "bad size %dx%d", W, H);
+  if (border < 0) return set_err(c, TVL1_EINVAL, "border must be >= 0 (got %d)", border);
+  if (fw < 1 || fh < 1) return set_err(c, TVL1_EINVAL, "bad flow size %dx%d", fw, fh);
+  // cv::remap's coordinates saturate to short
+  if ((int64_t)W + 2 * (int64_t)border > 32767 || (int64_t)H + 2 * (int64_t)border > 32767)
+    return set_err(c, TVL1_ESIZE, "canvas %lldx%lld above 32767", (long long)W + 2LL * border,
+                   (long long)H + 2LL * border);
+  const int CW = W + 2 * border, CH = H + 2 * border;
+  if (pitch < (size_t)W || dp < (size_t)CW) return set_err(c, TVL1_EINVAL, "pitch below the row size");
+  if (fpitch % 4 || fpitch < (size_t)fw * sizeof(float))
+    return set_err(c, TVL1_EINVAL, "flow pitch must be a multiple of 4 and >= 4 * fw");
+  const uintptr_t f0 = reinterpret_cast<uintptr_t>(frame), f1 = f0 + pitch * (size_t)(H - 1) + W;
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + dp * (size_t)(CH - 1) + CW;
+  if (f0 < d1 && d0 < f1) return set_err(c, TVL1_EINVAL, "dst overlaps frame");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  RemapArgs a;
+  a.frame = frame, a.pitch = pitch, a.W = W, a.H = H;
+  a.u = u, a.v = v, a.fpitch = fpitch / sizeof(float), a.fw = fw, a.fh = fh;
+  a.gain = gain, a.scale_x = (double)fw / W, a.scale_y = (double)fh / H;
+  a.border = border, a.dst = dst, a.dpitch = dp, a.CW = CW, a.CH = CH;
+  const size_t tok = xprof_begin(c, st);
+  hipLaunchKernelGGL(k_remap_flow_u8, grid_lanes(CW, CH, kRemapPx), kBlk2, 0, st, a);
+  xprof_end(c, st, tok, (double)W * H + (double)CW * CH + 8.0 * fw * fh);
+  HIP_TRY(c, hipGetLastError());
+  return TVL1_OK;
+}
+
 // tvl1_calc_host, and tvl1_calc_host_init with a host seed (u0, v0, row pitch ipitch bytes):
 // the seed is uploaded into the output staging planes, which the solve reads before its
 // last kernel writes them (the in/out flow of tvl1_calc_init)
@@ -3046,12 +3172,17 @@ void *tvl1_stream(tvl1_ctx *c) { return c ? (void *)c->own_stream : nullptr; }
 tvl1_status tvl1_set_profiling(tvl1_ctx *c, int32_t enable) {
   if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
   c->profiling = enable != 0;
+  if (!c->profiling) {   // slice-list marks still waiting for a solve do not outlive the switch
+    c->xmarks.clear();
+    c->xev_used = 0;
+  }
   return TVL1_OK;
 }
 
 void tvl1_destroy(tvl1_ctx *c) {
   if (!c) return;
   for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->xev_pool) (void)hipEventDestroy(e);
   (void)hipSetDevice(c->device);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   // hipFree waits for the device: callers' streams included

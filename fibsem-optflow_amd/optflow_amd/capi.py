@@ -230,6 +230,19 @@ def load_engine() -> C.CDLL:
                                      C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
     lib.tvl1_gather_flow.restype = C.c_int
+    # average-flow alignment of a slice list (added under ABI 9)
+    lib.tvl1_blend6_weights.argtypes = [C.POINTER(C.c_float)]
+    lib.tvl1_blend6_weights.restype = None
+    lib.tvl1_blend6_u8.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                   C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tvl1_blend6_u8.restype = C.c_int
+    lib.tvl1_half_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                 C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tvl1_half_u8.restype = C.c_int
+    lib.tvl1_remap_flow_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                       C.c_double, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tvl1_remap_flow_u8.restype = C.c_int
     lib.tvl1_stream.argtypes = [C.c_void_p]
     lib.tvl1_stream.restype = C.c_void_p
     lib.tvl1_set_profiling.argtypes = [C.c_void_p, C.c_int32]
@@ -466,6 +479,84 @@ class Engine:
                     "tvl1_gather_flow")
         return ou, ov
 
+    # ---- average-flow alignment of a slice list (tvl1_blend6_u8 ... tvl1_remap_flow_u8) ----
+    def blend6_u8(self, frames, pitches, w: int, h: int, dst: int, dst_pitch: int,
+                  stream: int = 0) -> None:
+        """tvl1_blend6_u8: six device u8 planes (pointers, pitches in bytes; the neighbours
+        i-3, i-2, i-1, i+1, i+2, i+3) -> their weighted mean, rounded half-to-even."""
+        if len(frames) != 6 or len(pitches) != 6:
+            raise ValueError("blend6_u8 takes six frames and six pitches")
+        fr = (C.c_void_p * 6)(*[C.c_void_p(int(f) or None) for f in frames])
+        pt = (C.c_size_t * 6)(*[int(p) for p in pitches])
+        self._check(self.lib.tvl1_blend6_u8(self.ctx, fr, pt, w, h, C.c_void_p(dst or None),
+                                            dst_pitch, C.c_void_p(stream) if stream else None),
+                    "tvl1_blend6_u8")
+
+    def half_u8(self, src: int, pitch: int, w: int, h: int, dst: int, dst_pitch: int,
+                stream: int = 0) -> None:
+        """tvl1_half_u8: the 2x2 mean of a w x h device plane (both even) -> w/2 x h/2."""
+        self._check(self.lib.tvl1_half_u8(self.ctx, C.c_void_p(src or None), pitch, w, h,
+                                          C.c_void_p(dst or None), dst_pitch,
+                                          C.c_void_p(stream) if stream else None), "tvl1_half_u8")
+
+    def remap_flow_u8(self, frame: int, pitch: int, w: int, h: int, du: int, dv: int,
+                      flow_pitch: int, fw: int, fh: int, gain: float, border: int, dst: int,
+                      dst_pitch: int, stream: int = 0) -> None:
+        """tvl1_remap_flow_u8: warp a w x h device frame by the fw x fh flow (times gain) onto a
+        (w + 2 border) x (h + 2 border) canvas."""
+        self._check(self.lib.tvl1_remap_flow_u8(self.ctx, C.c_void_p(frame or None), pitch, w, h,
+                                                C.c_void_p(du or None), C.c_void_p(dv or None),
+                                                flow_pitch, fw, fh, float(gain), border,
+                                                C.c_void_p(dst or None), dst_pitch,
+                                                C.c_void_p(stream) if stream else None),
+                    "tvl1_remap_flow_u8")
+
+    def align_slice_host(self, frames7, scale: float = 0.5, border: int = 0):
+        """One slice of the average-flow alignment on host arrays: frames7 = slices i-3 .. i+3
+        (u8, one size).  Uploads them, blends the six neighbours, pre-scales slice and blend
+        (scale 1: not at all; 0.5 with even sizes: tvl1_half_u8), solves slice -> blend and
+        warps the slice by the flow.  Returns (aligned (h + 2 border, w + 2 border) u8, u, v at
+        the solve's size).  Any other pre-scale is not done on the device: it raises."""
+        import torch
+        if len(frames7) != 7:
+            raise ValueError("align_slice_host takes the seven slices i-3 .. i+3")
+        fr = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames7]
+        h, w = fr[3].shape
+        if any(f.shape != (h, w) for f in fr):
+            raise ValueError("the seven slices must have one size")
+        if scale == 1:
+            halve = False
+        elif scale == 0.5 and w % 2 == 0 and h % 2 == 0:
+            halve = True
+        else:
+            raise ValueError(f"pre-scale {scale} of a {w}x{h} slice is not done on the device "
+                             "(scale 1, or 0.5 with even sizes)")
+        if border < 0:
+            raise ValueError("border must be >= 0")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d = [torch.from_numpy(f).to(dev) for f in fr]
+        fw, fh = (w // 2, h // 2) if halve else (w, h)
+        blend = torch.empty((h, w), dtype=torch.uint8, device=dev)
+        du = torch.empty((fh, fw), dtype=torch.float32, device=dev)
+        dv = torch.empty_like(du)
+        out = torch.empty((h + 2 * border, w + 2 * border), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        st = self.stream
+        nb = [d[k] for k in (0, 1, 2, 4, 5, 6)]
+        self.blend6_u8([t.data_ptr() for t in nb], [w] * 6, w, h, blend.data_ptr(), w, stream=st)
+        i0, i1 = d[3], blend
+        if halve:
+            i0 = torch.empty((fh, fw), dtype=torch.uint8, device=dev)
+            i1 = torch.empty_like(i0)
+            self.half_u8(d[3].data_ptr(), w, w, h, i0.data_ptr(), fw, stream=st)
+            self.half_u8(blend.data_ptr(), w, w, h, i1.data_ptr(), fw, stream=st)
+        self.calc_device(i0.data_ptr(), fw, i1.data_ptr(), fw, fw, fh, du.data_ptr(), dv.data_ptr(),
+                         4 * fw, stream=st, stats=False)
+        self.remap_flow_u8(d[3].data_ptr(), w, w, h, du.data_ptr(), dv.data_ptr(), 4 * fw, fw, fh,
+                           1.0 / scale, border, out.data_ptr(), w + 2 * border, stream=st)
+        torch.cuda.synchronize()
+        return out.cpu().numpy(), du.cpu().numpy(), dv.cpu().numpy()
+
     def close(self):
         if self.ctx:
             self.lib.tvl1_destroy(self.ctx)
@@ -481,6 +572,14 @@ class Engine:
 def epe(u, v, u_ref, v_ref) -> np.ndarray:
     """Per-pixel end-point error."""
     return np.sqrt((u.astype(np.float64) - u_ref) ** 2 + (v.astype(np.float64) - v_ref) ** 2)
+
+
+def blend6_weights() -> np.ndarray:
+    """tvl1_blend6_weights (host only): the six float32 weights of tvl1_blend6_u8, in
+    neighbour order i-3, i-2, i-1, i+1, i+2, i+3."""
+    w = (C.c_float * 6)()
+    load_engine().tvl1_blend6_weights(w)
+    return np.array(list(w), np.float32)
 
 
 def find_homography(src: np.ndarray, dst: np.ndarray, method: int = 8, thresh: float = 5.0):

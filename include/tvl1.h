@@ -287,6 +287,47 @@ tvl1_status tvl1_postprocess_affine(tvl1_ctx *ctx, float *u, float *v, size_t fl
                                     int32_t height, int32_t flow_output, const float affine[6],
                                     void *stream);
 
+/* ---- Average-flow alignment of a slice list (added under ABI 9; the reference's disabled
+ * average_flow / remap_and_save, optflow.cpp:180-226, 263-300; CLI "style": 2) ----
+ * For slice i: B = blend6 of slices i-3 .. i+3 without i, flow = tvl1_calc(F_i, B) on the
+ * pre-scaled pair, aligned = remap(F_i, flow).  All pointers are device pointers, all pitches
+ * bytes, every call asynchronous on `stream`; none touches the solver's scratch.  With
+ * profiling on they count into class 2 of the ctx's next solve: whichever solve that is, so
+ * a caller that wants a solve's own totals issues these calls on the ctx that solves next.
+ * At most 1024 such marks wait for a solve (later ones are dropped), and
+ * tvl1_set_profiling(ctx, 0) discards the ones still waiting.
+ *
+ * The blend's six weights, in neighbour order (i-3, i-2, i-1, i+1, i+2, i+3):
+ * float(float(exp(-d^2 / 4)) * s) with s = 0.5 / (exp(-9/4) + exp(-1) + exp(-1/4)) in double
+ * (cv::Vec6f times a double).  Their double sum is exactly 1.  Host only, no GPU. */
+void tvl1_blend6_weights(float w[6]);
+
+/* dst = saturate_u8(round-half-to-even(sum_k double(w_k) * frames[k])): the six neighbours'
+ * weighted mean with a double accumulator (exact: every weight is a multiple of 2^-28), then
+ * convertTo(CV_8U).  w x h planes. */
+tvl1_status tvl1_blend6_u8(tvl1_ctx *ctx, const uint8_t *const frames[6], const size_t pitches[6],
+                           int32_t w, int32_t h, uint8_t *dst, size_t dst_pitch, void *stream);
+
+/* cv::resize of a u8 plane at an exact 1/2 scale: dst = (a + b + c + d + 2) >> 2 over each
+ * 2x2 block.  w, h: the SOURCE size, both even (odd: TVL1_EINVAL); dst is w/2 x h/2. */
+tvl1_status tvl1_half_u8(tvl1_ctx *ctx, const uint8_t *src, size_t pitch, int32_t w, int32_t h,
+                         uint8_t *dst, size_t dst_pitch, void *stream);
+
+/* Warp a frame by a flow field onto a canvas of (w + 2 border) x (h + 2 border): canvas px
+ * (X, Y) shows frame coordinate (x, y) = (X - border, Y - border) and samples the frame at
+ * (x - U, y - V), where (U, V) is the flow at the nearest frame px: float(double(flow) * gain),
+ * the fw x fh planes (u, v) brought to w x h by cv::resize INTER_LINEAR (half-pixel centres)
+ * when the sizes differ.  The sample is cv::remap INTER_LINEAR on u8 with BORDER_CONSTANT 0:
+ * the map rounded to 1/32 px, four taps, 5-bit weights, each tap outside the frame counting
+ * 0; NaN or infinite flow gives 0.  Nothing of the frame's size is staged in memory.
+ * TVL1_EINVAL: a null pointer, a pitch below its row, flow_pitch not a multiple of 4,
+ * border < 0, fw or fh < 1, dst overlapping frame.  TVL1_ESIZE: w + 2 border or h + 2 border
+ * above 32767 (the map's coordinates saturate to short there, as in OpenCV). */
+tvl1_status tvl1_remap_flow_u8(tvl1_ctx *ctx, const uint8_t *frame, size_t pitch, int32_t w, int32_t h,
+                               const float *u, const float *v, size_t flow_pitch,
+                               int32_t fw, int32_t fh, double gain, int32_t border,
+                               uint8_t *dst, size_t dst_pitch, void *stream);
+
 /* Same on HOST memory: upload, solve, download, synchronize.
  * (GpuMat::upload optflow.cpp:315-316 ... download :475-476) */
 tvl1_status tvl1_calc_host(tvl1_ctx *ctx,
