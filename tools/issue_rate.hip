@@ -37,7 +37,10 @@ constexpr int ITER = 4096, CH = 8;
 // per lane (dependent: latency), 28 v_cndmask_b32_e32 (vcc), 29 v_sub_f32, 30 v_max_f32,
 // 31 v_cmp_gt_f32_e32 (vcc), 32 v_and_b32, 33 v_lshl_add_u32, 34 v_mad_u32_u24,
 // 35 v_cvt_f32_i32, 36 v_mul_f32_e64 with a neg modifier, 37 v_mov_b64, 38 v_fmac_f32,
-// 39 v_min_f32_e64 with abs, 40 v_ldexp_f32, 41 v_lshlrev_b32
+// 39 v_min_f32_e64 with abs, 40 v_ldexp_f32, 41 v_lshlrev_b32, 42 v_add_f32 + a not-taken
+// s_cbranch_execz (counted as one pair: the branch's price is the pair's minus v_add_f32's),
+// 43 v_add_f32 + a taken s_cbranch_execnz over 25 instructions (the iteration kernels' inline
+// fallback blocks; counted as one pair), 44 v_min3_f32 with abs
 template <int OP>
 __global__ __launch_bounds__(256) void k_rate(float *out, unsigned long long *cyc, float a, float b) {
   __shared__ float lds[256 * CH + 64];
@@ -128,6 +131,16 @@ __global__ __launch_bounds__(256) void k_rate(float *out, unsigned long long *cy
       if constexpr (OP == 39) asm volatile("v_min_f32_e64 %0, |%0|, %1" : "+v"(x[i]) : "v"(a));
       if constexpr (OP == 40) asm volatile("v_ldexp_f32 %0, %0, %1" : "+v"(x[i]) : "v"(a));
       if constexpr (OP == 41) asm volatile("v_lshlrev_b32 %0, 1, %0" : "+v"(x[i]));
+      if constexpr (OP == 42)
+        asm volatile("v_add_f32 %0, %0, %1\n s_cbranch_execz Lnt%=\n Lnt%=:" : "+v"(x[i]) : "v"(a));
+      if constexpr (OP == 43)
+        asm volatile(
+            "v_add_f32 %0, %0, %1\n s_cbranch_execnz Ltk%=\n"
+            ".rept 25\n v_add_f32 %0, %0, %1\n .endr\n"
+            "Ltk%=:"
+            : "+v"(x[i]) : "v"(a));
+      if constexpr (OP == 44)
+        asm volatile("v_min3_f32 %0, |%0|, |%1|, |%2|" : "+v"(x[i]) : "v"(a), "v"(b));
       if constexpr (OP == 27) {
         if (i == 0)
           for (int k = 0; k < CH; ++k) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(x[0]) : "v"(a), "v"(b));
@@ -259,5 +272,8 @@ int main() {
   run<39>("v_min_f32_e64 (abs)", CH, cus, out, cyc);
   run<40>("v_ldexp_f32", CH, cus, out, cyc);
   run<41>("v_lshlrev_b32", CH, cus, out, cyc);
+  run<42>("v_add_f32 + s_cbranch not taken (pair)", CH, cus, out, cyc);
+  run<43>("v_add_f32 + s_cbranch taken, skips 25", CH, cus, out, cyc);
+  run<44>("v_min3_f32 (abs)", CH, cus, out, cyc);
   return 0;
 }
