@@ -192,9 +192,10 @@ def check_margins(trace: np.ndarray, iterations: int) -> np.ndarray:
     at n + 2 iff r < 2, else at n + 4 iff r < 4, at n + 6 iff r < 6, ... (procOneScale's
     rule).  The thresholds are therefore t in {1, 2, 4, 6, ...} (those reachable
     before `iterations`), and a perturbation of the residual by a relative delta flips a
-    decision only if delta >= |r - t| / r for some t.  Returns that relative margin per check."""
+    decision only if delta >= |r - t| / r for some t.  Returns that relative margin per check
+    (inf for r = 0: no relative perturbation of a zero residual moves it)."""
     out = np.empty(len(trace))
     for i, (_, _, n, r) in enumerate(trace):
         ts = [1.0] + [float(t) for t in range(2, max(2, iterations - int(n)) + 1, 2)]
-        out[i] = min(abs(r - t) for t in ts) / r
+        out[i] = np.inf if r == 0 else min(abs(r - t) for t in ts) / r
     return out

@@ -58,3 +58,10 @@ def test_margin_thresholds_follow_procOneScale():
     tr = np.array([[0, 0, 1, 1.5], [0, 0, 3, 2.02], [0, 0, 5, 3.9], [0, 0, 295, 7.0]])
     m = checker.check_margins(tr, 300)
     np.testing.assert_allclose(m, [0.5 / 1.5, 0.02 / 2.02, 0.1 / 3.9, 3.0 / 7.0])   # 6 is out of reach at n = 295
+    # a zero residual (an identical pair, a 1 x 1 frame) is infinitely far from every threshold,
+    # and says so without a division warning
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        m0 = checker.check_margins(np.array([[0, 0, 1, 0.0], [0, 1, 1, 1.5]]), 300)
+    assert m0[0] == np.inf and m0[1] == pytest.approx(0.5 / 1.5)
