@@ -29,7 +29,13 @@
 //     "matches_file", "stats_json", "timing_json" (per-stage host seconds of strip jobs),
 //     "skip_existing", "pinned_host" (page-locked slices and
 //     flows, default off), "initialFlow" ([dx, dy]: with "useInitialFlow", the pair's ROIs
-//     are solved from that constant flow, tvl1_calc_init);
+//     are solved from that constant flow, tvl1_calc_init; or "auto": each ROI's constant is
+//     the integer drift tvl1_estimate_shift finds on the ROI views the solve sees, searched
+//     within "initialFlowMaxShift" px (default 32; per ROI at most min(W, H) / 4, and a ROI
+//     too small for a search of 1 px is solved unseeded).  There is no gate on the estimate:
+//     stats_json's "initial_flow_auto" carries sad / count, the summed and counted absolute
+//     differences over the overlap at the estimate, and sad_zero / count_zero, the same at
+//     (0, 0); a drift outside the search range shows as two means that barely differ);
 //   * "style": 2 (from_list below): the average-flow alignment of a slice list that the
 //     reference declares and keeps disabled; keys "slices" | "file_list", "border",
 //     "save_flow" (DESIGN 11, and 8 for where it departs from the disabled code).
@@ -144,10 +150,14 @@ bool resolve_features(const Value &im, const Value &args) {
 // build-only "initialFlow": [dx, dy] (px of the pre-scaled frame, flow from frame0 to frame1),
 // per image or global, honoured only with "useInitialFlow": true: the pair's ROIs are solved
 // by tvl1_calc_init from that constant flow.  "useInitialFlow" alone stays without effect,
-// as in the reference (optflow.cpp:512, never passed to create()).
+// as in the reference (optflow.cpp:512, never passed to create()).  "initialFlow": "auto" is
+// the same with a constant found per ROI (tvl1_estimate_shift within "initialFlowMaxShift" px,
+// default 32, per image or global); any other value of the key stays inert.
 struct InitFlow {
   bool on = false;
   float dx = 0.f, dy = 0.f;
+  bool automatic = false;
+  int max_shift = 0;
 };
 const char *const kInitFlowFeatures =
     "initialFlow cannot be combined with feature alignment (features, a pair without ROIs, or "
@@ -156,6 +166,11 @@ InitFlow initial_flow_of(const Value &im, const Value &args) {
   InitFlow f;
   if (!im.get("useInitialFlow", args.get("useInitialFlow", false).asBool()).asBool()) return f;
   const Value &v = im.isMember("initialFlow") ? im["initialFlow"] : args["initialFlow"];
+  if (v.isString() && v.asString() == "auto") {
+    f.on = f.automatic = true;
+    f.max_shift = im.get("initialFlowMaxShift", args.get("initialFlowMaxShift", 32).asInt()).asInt();
+    return f;
+  }
   if (!v.isArray() || v.size() != 2) return f;
   f.on = true;
   f.dx = v[0].asFloat();
@@ -540,7 +555,7 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
                    const float *affine, PairResult &res, std::string &err) {
   const int W = r0.width, H = r0.height;
   tvl1_params prm = generate_TV_args(im, args);
-  const InitFlow init = initial_flow_of(im, args);
+  InitFlow init = initial_flow_of(im, args);
   if (const tvl1_status s = tvl1_set_params(dc.ctx, &prm); s != TVL1_OK) {
     err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
     return false;
@@ -549,6 +564,25 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
   const uint8_t *a = dc.d0 + (size_t)r0.y * f0.width + r0.x;
   const uint8_t *b = dc.d1 + (size_t)r1.y * f1.width + r1.x;
   const size_t pitch1 = (size_t)f1.width;
+  // "initialFlow": "auto": the ROI's integer drift, on the views the solve sees
+  tvl1_shift shift;
+  memset(&shift, 0, sizeof shift);
+  const bool auto_seed = init.automatic;
+  int auto_R = 0;
+  if (auto_seed) {
+    auto_R = std::min(std::min(init.max_shift, 128), std::min(W, H) / 4);
+    if (auto_R < 1) {
+      auto_R = 0;
+      init.on = false;   // too small to search: solved unseeded
+    } else {
+      if (const tvl1_status s = tvl1_estimate_shift(dc.ctx, a, pitch, b, pitch1, W, H, auto_R, &shift, dc.stream);
+          s != TVL1_OK) {
+        err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
+        return false;
+      }
+      init.dx = (float)shift.dx, init.dy = (float)shift.dy;
+    }
+  }
   const size_t fp = (size_t)W * sizeof(float);
   tvl1_stats st;
   memset(&st, 0, sizeof st);
@@ -573,6 +607,15 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
     if (init.on) {
       sv["initial_flow"][0] = (double)init.dx;
       sv["initial_flow"][1] = (double)init.dy;
+    }
+    if (auto_seed) {
+      sv["initial_flow_auto"]["max_shift"] = auto_R;
+      if (auto_R) {
+        sv["initial_flow_auto"]["sad"] = (int64_t)shift.sad;
+        sv["initial_flow_auto"]["count"] = (int64_t)shift.count;
+        sv["initial_flow_auto"]["sad_zero"] = (int64_t)shift.sad_zero;
+        sv["initial_flow_auto"]["count_zero"] = (int64_t)shift.count_zero;
+      }
     }
     res.stats["solves"].append(sv);
   };
@@ -1178,7 +1221,10 @@ static int from_file(Value &args, bool plan_only) {
           pl["output_type"] = output_type_of(im, args);
           pl["features"] = resolve_features(im, args);
           pl["strip_batch"] = (bool)batch_ok[i];   // solved in a tvl1_calc_batch chunk
-          if (const InitFlow f0 = initial_flow_of(im, args); f0.on) {   // tvl1_calc_init per ROI
+          if (const InitFlow f0 = initial_flow_of(im, args); f0.automatic) {
+            pl["initialFlow"] = "auto";   // tvl1_estimate_shift, then tvl1_calc_init, per ROI
+            pl["initialFlowMaxShift"] = f0.max_shift;
+          } else if (f0.on) {   // tvl1_calc_init per ROI
             pl["initialFlow"][0] = (double)f0.dx;
             pl["initialFlow"][1] = (double)f0.dy;
           }

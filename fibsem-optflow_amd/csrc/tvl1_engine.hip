@@ -26,6 +26,7 @@
 #include "tvl1_batch.hpp"
 #include "tvl1_align.hpp"
 #include "tvl1_stack.hpp"
+#include "tvl1_shift.hpp"
 
 // the iteration passes are compiled in tvl1_passes.hip (another instruction scheduler)
 namespace tvl1k {
@@ -175,6 +176,8 @@ struct tvl1_ctx {
   char *align_scratch = nullptr;        // tvl1_find_alignment's pyramid, keys, descriptors
   size_t align_bytes = 0;
   int4 *align_pat = nullptr;            // the rBRIEF pair pattern (device, set once)
+  char *shift_scratch = nullptr;        // tvl1_estimate_shift's pyramids, tables and records
+  size_t shift_bytes = 0;
   int bnblk = 0;                        // partials per pair
   int check = 0;             // TVL1_CHECK=1: synchronise + check after every launch (diagnostics)
 
@@ -3049,6 +3052,169 @@ tvl1_status tvl1_remap_flow_u8(tvl1_ctx *c, const uint8_t *frame, size_t pitch, 
   return TVL1_OK;
 }
 
+// ---- Integer drift estimate (added under ABI 9; kernels in tvl1_shift.hpp) ----
+static constexpr int kShiftLevels = 8;    // max_shift <= 128: L <= 5
+static constexpr int kShiftChunk = 256;   // pairs per launch
+
+// I0 rows per wavefront of k_sad_shifts: long segments (the 2r halo rows of I1 are read again
+// by the next segment) unless the launch would leave the device short of wavefronts
+static int shift_seg(int w, int h, int n) {
+  const long bands = (w + kShiftBand - 1) / kShiftBand;
+  int seg = 64;
+  while (seg > 8 && bands * n * ((h + seg - 1) / seg) < 8192) seg >>= 1;
+  return seg;
+}
+
+static void launch_sad_shifts(const ShiftSadArgs &a, int n, int r, bool zero, hipStream_t st) {
+  const int segs = (a.h + a.seg - 1) / a.seg;
+  const dim3 grid((unsigned)((a.w + kShiftBand - 1) / kShiftBand), (unsigned)n, (unsigned)((segs + 3) / 4));
+#define SHIFT_LAUNCH(R)                                                                    \
+  case R:                                                                                  \
+    if (zero) hipLaunchKernelGGL((k_sad_shifts<R, true>), grid, kBlk2, 0, st, a);          \
+    else hipLaunchKernelGGL((k_sad_shifts<R, false>), grid, kBlk2, 0, st, a);              \
+    break;
+  switch (r) {
+    SHIFT_LAUNCH(1)
+    SHIFT_LAUNCH(2)
+    SHIFT_LAUNCH(3)
+    SHIFT_LAUNCH(4)
+  }
+#undef SHIFT_LAUNCH
+}
+
+static tvl1_status check_shift_frames(tvl1_ctx *c, const uint8_t *I0, size_t p0, const uint8_t *I1,
+                                      size_t p1, int32_t w, int32_t h, const void *out) {
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  if (!I0) return set_err(c, TVL1_EINVAL, "I0 is NULL");
+  if (!I1) return set_err(c, TVL1_EINVAL, "I1 is NULL");
+  if (!out) return set_err(c, TVL1_EINVAL, "out is NULL");
+  if (w <= 0 || h <= 0) return set_err(c, TVL1_ESIZE, "bad size %dx%d", w, h);
+  if ((int64_t)w * h > ((int64_t)1 << 26))
+    return set_err(c, TVL1_ESIZE, "w*h = %lld above 2^26", (long long)w * h);
+  if (p0 < (size_t)w) return set_err(c, TVL1_EINVAL, "pitch0 below the row size");
+  if (p1 < (size_t)w) return set_err(c, TVL1_EINVAL, "pitch1 below the row size");
+  return TVL1_OK;
+}
+
+static tvl1_status ensure_shift_scratch(tvl1_ctx *c, size_t need, hipStream_t st) {
+  order_streams(c, st);
+  if (!c->retired.empty()) reap_retired(c, false);
+  if (need <= c->shift_bytes) return TVL1_OK;
+  return arena_alloc(c, &c->shift_scratch, &c->shift_bytes, std::max<size_t>(need, 64 << 10), st);
+}
+
+tvl1_status tvl1_sad_shifts_u8(tvl1_ctx *c, const uint8_t *I0, size_t p0, const uint8_t *I1, size_t p1,
+                               int32_t w, int32_t h, int32_t cx, int32_t cy, int32_t radius,
+                               uint64_t *sad, void *stream) {
+  tvl1_status s = check_shift_frames(c, I0, p0, I1, p1, w, h, sad);
+  if (s != TVL1_OK) return s;
+  if (radius < 1 || radius > kShiftMaxR)
+    return set_err(c, TVL1_EINVAL, "radius must be in 1..4 (got %d)", radius);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  TVL1_TRY(ensure_shift_scratch(c, kShiftSlots * sizeof(uint64_t), st));
+  unsigned long long *table = reinterpret_cast<unsigned long long *>(c->shift_scratch);
+  HIP_TRY(c, hipMemsetAsync(table, 0, kShiftSlots * sizeof(uint64_t), st));
+  // a centre further out than the frame has no overlap at any of its shifts; so has this one
+  ShiftSadArgs a{I0, I1, p0, p1, 0, 0, w, h, nullptr, std::max(-(w + 8), std::min(w + 8, cx)),
+                 std::max(-(h + 8), std::min(h + 8, cy)), shift_seg(w, h, 1), table};
+  launch_sad_shifts(a, 1, radius, false, st);
+  HIP_TRY(c, hipGetLastError());
+  const int D = 2 * radius + 1;
+  HIP_TRY(c, hipMemcpyAsync(sad, table, (size_t)D * D * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return TVL1_OK;
+}
+
+// One chunk of pairs: pyramid, then per level table and selection, all enqueued on st
+static tvl1_status shift_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size_t p0, size_t s0,
+                               const uint8_t *I1, size_t p1, size_t s1, int w, int h, int R,
+                               tvl1_shift *out, hipStream_t st) {
+  int L = 0;
+  while (((R + (1 << L) - 1) >> L) > kShiftMaxR) ++L;
+  int ws[kShiftLevels], hs[kShiftLevels];
+  size_t lp[kShiftLevels], off[kShiftLevels], one = 0;   // level planes of one frame of one pair
+  ws[0] = w, hs[0] = h;
+  for (int l = 1; l <= L; ++l) {
+    ws[l] = ws[l - 1] / 2, hs[l] = hs[l - 1] / 2;
+    lp[l] = align_up((size_t)ws[l], 16);
+    off[l] = one;
+    one += align_up(lp[l] * hs[l], 256);
+  }
+  const int n0 = s0 ? n : 1, n1 = s1 ? n : 1;   // a frame shared by every pair has one pyramid
+  const size_t tab_b = align_up((size_t)(L + 1) * n * kShiftSlots * sizeof(uint64_t), 256);
+  const size_t base_b = align_up((size_t)(L + 1) * n * sizeof(int2), 256);
+  const size_t rec_b = align_up((size_t)n * sizeof(tvl1_shift), 256);
+  TVL1_TRY(ensure_shift_scratch(c, tab_b + base_b + rec_b + one * (size_t)(n0 + n1), st));
+  char *p = c->shift_scratch;
+  unsigned long long *tables = reinterpret_cast<unsigned long long *>(p);
+  int2 *bases = reinterpret_cast<int2 *>(p + tab_b);
+  tvl1_shift *recs = reinterpret_cast<tvl1_shift *>(p + tab_b + base_b);
+  uint8_t *pyr0 = reinterpret_cast<uint8_t *>(p + tab_b + base_b + rec_b), *pyr1 = pyr0 + one * n0;
+  HIP_TRY(c, hipMemsetAsync(tables, 0, tab_b, st));
+  // level l of frame f: plane, pitch and pair stride
+  auto plane = [&](int f, int l, const uint8_t *&q, size_t &pitch, size_t &stride) {
+    if (l == 0) q = f ? I1 : I0, pitch = f ? p1 : p0, stride = f ? s1 : s0;
+    else q = (f ? pyr1 : pyr0) + off[l], pitch = lp[l], stride = (f ? s1 : s0) ? one : 0;
+  };
+  for (int l = 1; l <= L; ++l)
+    for (int f = 0; f < 2; ++f) {
+      const uint8_t *src, *dst;
+      size_t sp, ss, dp, ds;
+      plane(f, l - 1, src, sp, ss);
+      plane(f, l, dst, dp, ds);
+      const dim3 grid((unsigned)(((ws[l] + kStackPx - 1) / kStackPx + 63) / 64), (unsigned)(f ? n1 : n0),
+                      (unsigned)((hs[l] + 3) / 4));
+      hipLaunchKernelGGL(k_shift_half, grid, kBlk2, 0, st, src, sp, ss, ws[l], hs[l],
+                         const_cast<uint8_t *>(dst), dp, ds);
+    }
+  for (int l = L; l >= 0; --l) {
+    const int r = l == L ? (R + (1 << L) - 1) >> L : 1;
+    unsigned long long *table = tables + (size_t)l * n * kShiftSlots;
+    const int2 *base = l == L ? nullptr : bases + (size_t)l * n;
+    ShiftSadArgs a{};
+    plane(0, l, a.I0, a.p0, a.s0);
+    plane(1, l, a.I1, a.p1, a.s1);
+    a.w = ws[l], a.h = hs[l], a.base = base, a.cx = 0, a.cy = 0;
+    a.seg = shift_seg(ws[l], hs[l], n), a.table = table;
+    launch_sad_shifts(a, n, r, l == 0, st);
+    ShiftSelArgs b{table, base, ws[l], hs[l], r, (R + (1 << l) - 1) >> l, l == 0, L + 1,
+                   l > 0 ? bases + (size_t)(l - 1) * n : nullptr, recs};
+    hipLaunchKernelGGL(k_shift_select, dim3(1, (unsigned)n), dim3(64), 0, st, b);
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(out, recs, (size_t)n * sizeof(tvl1_shift), hipMemcpyDeviceToHost, st));
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_estimate_shift_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t p0, size_t s0,
+                                      const uint8_t *I1, size_t p1, size_t s1, int32_t w, int32_t h,
+                                      int32_t R, tvl1_shift *out, void *stream) {
+  tvl1_status s = check_shift_frames(c, I0, p0, I1, p1, w, h, out);
+  if (s != TVL1_OK) return s;
+  if (n < 1) return set_err(c, TVL1_EINVAL, "n must be >= 1 (got %d)", n);
+  if (R < 1 || R > 128) return set_err(c, TVL1_EINVAL, "max_shift must be in 1..128 (got %d)", R);
+  if (4 * R > std::min(w, h))
+    return set_err(c, TVL1_EINVAL, "4 * max_shift = %d above min(w, h) = %d", 4 * R, std::min(w, h));
+  if (n > 1 && ((s0 != 0 && s0 < p0 * (size_t)(h - 1) + w) || (s1 != 0 && s1 < p1 * (size_t)(h - 1) + w)))
+    return set_err(c, TVL1_EINVAL, "pair_stride0 / pair_stride1 must be 0 or cover one image");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  for (int32_t b = 0; b < n; b += kShiftChunk) {
+    // the next chunk re-lays the workspace: in stream order behind this one's record copy
+    const int m = std::min(kShiftChunk, n - b);
+    TVL1_TRY(shift_chunk(c, m, I0 + (size_t)b * s0, p0, s0, I1 + (size_t)b * s1, p1, s1, w, h, R,
+                         out + b, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_estimate_shift(tvl1_ctx *c, const uint8_t *I0, size_t p0, const uint8_t *I1, size_t p1,
+                                int32_t w, int32_t h, int32_t R, tvl1_shift *out, void *stream) {
+  return tvl1_estimate_shift_batch(c, 1, I0, p0, 0, I1, p1, 0, w, h, R, out, stream);
+}
+
 // tvl1_calc_host, and tvl1_calc_host_init with a host seed (u0, v0, row pitch ipitch bytes):
 // the seed is uploaded into the output staging planes, which the solve reads before its
 // last kernel writes them (the in/out flow of tvl1_calc_init)
@@ -3192,6 +3358,7 @@ void tvl1_destroy(tvl1_ctx *c) {
   if (c->map_scratch) (void)hipFree(c->map_scratch);
   if (c->gather_scratch) (void)hipFree(c->gather_scratch);
   if (c->small_scratch) (void)hipFree(c->small_scratch);
+  if (c->shift_scratch) (void)hipFree(c->shift_scratch);
   for (auto &r : c->retired) free_retired(r);
   if (c->align_pat) (void)hipFree(c->align_pat);
   if (c->pinned) (void)hipHostFree(c->pinned);

@@ -81,6 +81,25 @@ class TVL1AlignParams(C.Structure):
     ]
 
 
+class TVL1Shift(C.Structure):
+    """tvl1_shift (include/tvl1.h): the record of tvl1_estimate_shift."""
+    _fields_ = [
+        ("dx", C.c_int32),
+        ("dy", C.c_int32),
+        ("levels", C.c_int32),
+        ("reserved", C.c_int32),
+        ("sad", C.c_uint64),
+        ("count", C.c_uint64),
+        ("sad_zero", C.c_uint64),
+        ("count_zero", C.c_uint64),
+    ]
+
+
+def shift_dict(r: TVL1Shift) -> dict:
+    return dict(dx=int(r.dx), dy=int(r.dy), levels=int(r.levels), sad=int(r.sad),
+                count=int(r.count), sad_zero=int(r.sad_zero), count_zero=int(r.count_zero))
+
+
 # generate_TV_args defaults, /root/reference/src/optflow.cpp:503-512
 DEFAULTS = dict(tau=0.25, lambda_=0.05, theta=0.3, nscales=10, warps=5, epsilon=0.01,
                 iterations=300, scale_step=0.8, gamma=0.0, use_initial_flow=0,
@@ -243,6 +262,20 @@ def load_engine() -> C.CDLL:
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
                                        C.c_double, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.tvl1_remap_flow_u8.restype = C.c_int
+    # integer drift estimate (added under ABI 9)
+    lib.tvl1_estimate_shift.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                        C.c_int32, C.c_int32, C.c_int32, C.POINTER(TVL1Shift),
+                                        C.c_void_p]
+    lib.tvl1_estimate_shift.restype = C.c_int
+    lib.tvl1_estimate_shift_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(TVL1Shift), C.c_void_p]
+    lib.tvl1_estimate_shift_batch.restype = C.c_int
+    lib.tvl1_sad_shifts_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_void_p]
+    lib.tvl1_sad_shifts_u8.restype = C.c_int
     lib.tvl1_stream.argtypes = [C.c_void_p]
     lib.tvl1_stream.restype = C.c_void_p
     lib.tvl1_set_profiling.argtypes = [C.c_void_p, C.c_int32]
@@ -556,6 +589,58 @@ class Engine:
                            1.0 / scale, border, out.data_ptr(), w + 2 * border, stream=st)
         torch.cuda.synchronize()
         return out.cpu().numpy(), du.cpu().numpy(), dv.cpu().numpy()
+
+    # ---- integer drift estimate (tvl1_estimate_shift ... tvl1_sad_shifts_u8) ----
+    def estimate_shift(self, dI0: int, pitch0: int, dI1: int, pitch1: int, w: int, h: int,
+                       max_shift: int, stream: int = 0) -> dict:
+        """tvl1_estimate_shift on device u8 frames (pitches in bytes): the integer (dx, dy) with
+        I1(x + d) ~= I0(x), |dx|, |dy| <= max_shift, and the sums behind it, as a dict."""
+        r = TVL1Shift()
+        self._check(self.lib.tvl1_estimate_shift(self.ctx, C.c_void_p(dI0 or None), pitch0,
+                                                 C.c_void_p(dI1 or None), pitch1, w, h, max_shift,
+                                                 C.byref(r), C.c_void_p(stream) if stream else None),
+                    "tvl1_estimate_shift")
+        return shift_dict(r)
+
+    def estimate_shift_batch(self, n: int, dI0: int, pitch0: int, stride0: int, dI1: int,
+                             pitch1: int, stride1: int, w: int, h: int, max_shift: int,
+                             stream: int = 0) -> list:
+        """tvl1_estimate_shift_batch: n pairs of one size, pair b at base + b*stride (bytes; 0 =
+        one frame for every pair).  One dict per pair."""
+        rs = (TVL1Shift * max(1, n))()
+        self._check(self.lib.tvl1_estimate_shift_batch(self.ctx, n, C.c_void_p(dI0 or None), pitch0,
+                                                       stride0, C.c_void_p(dI1 or None), pitch1,
+                                                       stride1, w, h, max_shift, rs,
+                                                       C.c_void_p(stream) if stream else None),
+                    "tvl1_estimate_shift_batch")
+        return [shift_dict(rs[b]) for b in range(n)]
+
+    def sad_shifts_u8(self, dI0: int, pitch0: int, dI1: int, pitch1: int, w: int, h: int,
+                      cx: int, cy: int, radius: int, stream: int = 0) -> np.ndarray:
+        """tvl1_sad_shifts_u8: S(cx + dx, cy + dy) for dx, dy in [-radius, radius] as a
+        (2r + 1, 2r + 1) uint64 array indexed [dy + r, dx + r]."""
+        d = 2 * max(1, min(4, int(radius))) + 1
+        out = np.zeros((d, d), np.uint64)
+        self._check(self.lib.tvl1_sad_shifts_u8(self.ctx, C.c_void_p(dI0 or None), pitch0,
+                                                C.c_void_p(dI1 or None), pitch1, w, h, cx, cy,
+                                                radius, out.ctypes.data,
+                                                C.c_void_p(stream) if stream else None),
+                    "tvl1_sad_shifts_u8")
+        return out
+
+    def estimate_shift_host(self, I0: np.ndarray, I1: np.ndarray, max_shift: int) -> dict:
+        """estimate_shift on host u8 arrays of one size: uploads them and calls."""
+        import torch
+        I0 = np.array(I0, dtype=np.uint8, order="C")   # copies: torch wants writable arrays
+        I1 = np.array(I1, dtype=np.uint8, order="C")
+        if I1.shape != I0.shape:
+            raise ValueError("I0 and I1 must have the same size")
+        h, w = I0.shape
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d0, d1 = torch.from_numpy(I0).to(dev), torch.from_numpy(I1).to(dev)
+        torch.cuda.synchronize()
+        return self.estimate_shift(d0.data_ptr(), w, d1.data_ptr(), w, w, h, max_shift,
+                                   stream=self.stream)
 
     def close(self):
         if self.ctx:

@@ -328,6 +328,48 @@ tvl1_status tvl1_remap_flow_u8(tvl1_ctx *ctx, const uint8_t *frame, size_t pitch
                                int32_t fw, int32_t fh, double gain, int32_t border,
                                uint8_t *dst, size_t dst_pitch, void *stream);
 
+/* ---- Integer drift estimate of a frame pair (added under ABI 9) ----
+ * The integer translation d = (dx, dy) with I1(x + d) ~= I0(x) (the flow's convention), for
+ * seeding tvl1_calc_init when a stage drift lies outside what the unseeded solve captures.
+ * Cost of a shift on a level of w x h px: S(d) = sum |I0(x, y) - I1(x + dx, y + dy)| over the
+ * overlap, N(d) = (w - |dx|)(h - |dy|) px; a is better than b iff S_a N_b < S_b N_a (the mean
+ * absolute differences, compared exactly in 64-bit integers), then the smaller dx^2 + dy^2,
+ * then dy, then dx.  Pyramid: L = the smallest integer with ceil(R / 2^L) <= 4, R = max_shift;
+ * each level is the one before, cropped to even sizes, under tvl1_half_u8's 2x2 mean.  Search:
+ * every shift of [-R_L, R_L]^2 on level L, R_l = ceil(R / 2^l); 2 d_(l+1) + {-1, 0, 1}^2 within
+ * R_l on level l < L; level 0 also tries (0, 0).  No float anywhere: any profile, any
+ * arithmetic mode.  A true shift outside max_shift returns some in-range shift whose mean
+ * difference is barely below (0, 0)'s: compare sad / count with sad_zero / count_zero. */
+typedef struct tvl1_shift {
+  int32_t dx, dy, levels, reserved;   /* levels = L + 1 */
+  uint64_t sad, count;                /* S and N of the result at level 0 */
+  uint64_t sad_zero, count_zero;      /* S and N of (0, 0) at level 0 */
+} tvl1_shift;
+
+/* I0, I1: device u8 frames of w x h (ROI views allowed: any pointer, any pitch >= w); out: one
+ * HOST record.  1 <= max_shift <= 128 and 4 max_shift <= min(w, h), else TVL1_EINVAL; w h >
+ * 2^26 is TVL1_ESIZE.  The whole search is enqueued on `stream` without a host round trip; the
+ * call returns once the record has arrived (it synchronizes the stream). */
+tvl1_status tvl1_estimate_shift(tvl1_ctx *ctx, const uint8_t *I0, size_t pitch0,
+                                const uint8_t *I1, size_t pitch1, int32_t w, int32_t h,
+                                int32_t max_shift, tvl1_shift *out, void *stream);
+
+/* n pairs of one size, laid out as tvl1_calc_batch's (pair b at I0 + b*pair_stride0, I1 +
+ * b*pair_stride1 bytes; 0 = the same frame for every pair); out: n HOST records, each equal to
+ * tvl1_estimate_shift's of that pair.  Up to 256 pairs share every launch. */
+tvl1_status tvl1_estimate_shift_batch(tvl1_ctx *ctx, int32_t n, const uint8_t *I0, size_t pitch0,
+                                      size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                                      size_t pair_stride1, int32_t w, int32_t h,
+                                      int32_t max_shift, tvl1_shift *out, void *stream);
+
+/* The estimate's cost kernel as a call of its own: sad[(dy + r) (2r + 1) + (dx + r)] =
+ * S(cx + dx, cy + dy) for dx, dy in [-r, r], r = radius in 1 .. 4 (else TVL1_EINVAL), on one
+ * level (no pyramid).  A shift whose overlap is empty reports 0.  sad: (2r + 1)^2 HOST values;
+ * synchronous on stream. */
+tvl1_status tvl1_sad_shifts_u8(tvl1_ctx *ctx, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
+                               size_t pitch1, int32_t w, int32_t h, int32_t cx, int32_t cy,
+                               int32_t radius, uint64_t *sad, void *stream);
+
 /* Same on HOST memory: upload, solve, download, synchronize.
  * (GpuMat::upload optflow.cpp:315-316 ... download :475-476) */
 tvl1_status tvl1_calc_host(tvl1_ctx *ctx,
