@@ -1,7 +1,8 @@
 /* TEST INFRASTRUCTURE: drives the oracle under ASan + UBSan (`make -C oracle asan`,
  * tests/test_host_hardening_cpu.py::test_oracle_under_asan).  Solves small synthetic pairs
  * at odd sizes through every code path of the restatement: both profiles, gamma, median,
- * fixed work, a pyramid that bottoms out, and 1x1 / 16x16 edge sizes. */
+ * fixed work, a pyramid that bottoms out, 1x1 / 16x16 edge sizes, and the seeded entry in
+ * both arithmetics (a pitched seed whose taps leave the frame on every side). */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -48,6 +49,31 @@ int main(void) {
       }
       orc_postprocess(u, v, sizeof(float) * (size_t)w, b, (size_t)w, w, h, 1);
     }
+    /* orc_tvl1_calc_init: IEEE and fma, seed rows padded by 3 floats, flows past every edge */
+    const size_t sp = (size_t)w + 3;
+    float *u0 = malloc(sizeof(float) * sp * h), *v0 = malloc(sizeof(float) * sp * h);
+    for (int y = 0; y < h; ++y)
+      for (size_t x = 0; x < sp; ++x) {
+        u0[y * sp + x] = (float)((int)((x * 7 + (size_t)y * 3) % 23) - 11) * 0.75f;
+        v0[y * sp + x] = (float)((int)((x * 5 + (size_t)y * 11) % 19) - 9) * 1.25f;
+      }
+    for (int fm = 0; fm <= 2; fm += 2) {
+      tvl1_params p = {0.25, 0.05, 0.3, 10, 3, 0.01, 300, 0.8, 0.0, 0, 1, 0, 0, 30, 10};
+      p.fast_math = fm;
+      tvl1_stats st;
+      memset(&st, 0, sizeof st);
+      const int rc = orc_tvl1_calc_init(&p, a, (size_t)w, b, (size_t)w, w, h, u0, v0,
+                                        sizeof(float) * sp, u, v, sizeof(float) * (size_t)w, &st);
+      p.profile = 1;
+      const int rc1 = orc_tvl1_calc_init(&p, a, (size_t)w, b, (size_t)w, w, h, u0, v0,
+                                         sizeof(float) * sp, u, v, sizeof(float) * (size_t)w, &st);
+      if (rc != 0 || rc1 != TVL1_EINVAL) {
+        fprintf(stderr, "%dx%d seeded fast_math %d: status %d, profile 1: %d\n", w, h, fm, rc, rc1);
+        ++fails;
+      }
+    }
+    free(u0);
+    free(v0);
     free(a);
     free(b);
     free(u);

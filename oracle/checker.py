@@ -32,6 +32,12 @@ def load_oracle(so: str | Path | None = None) -> C.CDLL:
                                       C.POINTER(C.c_float), C.c_size_t, C.c_int, C.c_int,
                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t,
                                       C.POINTER(TVL1Stats)]
+    lib.orc_tvl1_calc_init.restype = C.c_int
+    lib.orc_tvl1_calc_init.argtypes = [C.POINTER(TVL1Params), C.POINTER(C.c_uint8), C.c_size_t,
+                                       C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.c_int,
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t,
+                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t,
+                                       C.POINTER(TVL1Stats)]
     lib.orc_num_threads.restype = C.c_int
     lib.orc_set_num_threads.argtypes = [C.c_int]
     return lib
@@ -39,9 +45,10 @@ def load_oracle(so: str | Path | None = None) -> C.CDLL:
 
 def oracle_calc(I0: np.ndarray, I1: np.ndarray, params: TVL1Params | None = None,
                 warp_iters: bool = True, threads: int | None = None,
-                so: str | Path | None = None):
+                so: str | Path | None = None, init=None):
     """Run the CPU restatement on host u8 images (or float32 images: tvl1_calc_f32's
-    contract, values scaled by 255); returns (u, v, stats, warp_iters)."""
+    contract, values scaled by 255); returns (u, v, stats, warp_iters).  init = (u0, v0):
+    the solve of tvl1_calc_init from that float32 seed (u8 frames, profile 0)."""
     lib = load_oracle(so)
     if threads:
         lib.orc_set_num_threads(int(threads))
@@ -60,7 +67,16 @@ def oracle_calc(I0: np.ndarray, I1: np.ndarray, params: TVL1Params | None = None
         wi = np.full(cap, -1, np.int32)
         st.warp_iterations = wi.ctypes.data_as(C.POINTER(C.c_int32))
         st.warp_iterations_capacity = cap
-    if f32:
+    if init is not None:
+        if f32:
+            raise TypeError("oracle: the seeded solve takes u8 frames")
+        u0, v0 = (np.ascontiguousarray(a, dtype=np.float32) for a in init)
+        if u0.shape != (h, w) or v0.shape != (h, w):
+            raise ValueError("oracle: the seed must have the frame's shape")
+        rc = lib.orc_tvl1_calc_init(C.byref(params), _u8_ptr(I0), w, _u8_ptr(I1), w, w, h,
+                                    _f32_ptr(u0), _f32_ptr(v0), 4 * w, _f32_ptr(u), _f32_ptr(v),
+                                    4 * w, C.byref(st))
+    elif f32:
         rc = lib.orc_tvl1_calc_f32(C.byref(params), _f32_ptr(I0), 4 * w, _f32_ptr(I1), 4 * w, w,
                                    h, _f32_ptr(u), _f32_ptr(v), 4 * w, C.byref(st))
     else:
@@ -166,16 +182,16 @@ def oracle_postprocess_affine(u: np.ndarray, v: np.ndarray, I1: np.ndarray, flow
 # ---- stopping-rule robustness: the oracle's per-check
 # error / scaledEps trace and an alternative residual accumulation order
 def oracle_check_trace(I0: np.ndarray, I1: np.ndarray, params: TVL1Params | None = None,
-                       residual_mode: int = 0, cap: int = 1 << 16):
+                       residual_mode: int = 0, cap: int = 1 << 16, init=None):
     """oracle_calc with every check recorded: returns (u, v, stats, warp_iters, trace) where
     trace is an (n, 4) array of (level, warp, n, error / scaledEps).  residual_mode 1 sums the
-    residual in float, rows reversed (orc_set_residual_mode)."""
+    residual in float, rows reversed (orc_set_residual_mode).  init: oracle_calc's seed."""
     lib = load_oracle()
     buf = np.zeros((cap, 4), np.float64)
     lib.orc_set_residual_mode(int(residual_mode))
     lib.orc_set_check_trace(buf.ctypes.data_as(C.c_void_p), cap)
     try:
-        u, v, st, wi = oracle_calc(I0, I1, params)
+        u, v, st, wi = oracle_calc(I0, I1, params, init=init)
         n = int(lib.orc_check_trace_count())
     finally:
         lib.orc_set_check_trace(None, 0)

@@ -496,12 +496,18 @@ typedef struct {
   float *I0, *I1, *u1, *u2, *u3;
 } level_bufs;
 
-/* [A.1]-[A.4] calc / calcImpl / procOneScale; u8 inputs (pitch in px) or f32 (bytes). */
+/* [A.1]-[A.4] calc / calcImpl / procOneScale; u8 inputs (pitch in px) or f32 (bytes).
+ * seeded: the solve starts from (u0, v0) (row pitch init_pitch bytes) instead of zero
+ * [A.2b]; the seed may alias the flow (it is read before the flow is written). */
 static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const void *I1,
-                   size_t pitch1, int f32, int w, int h, float *u, float *v,
-                   size_t flow_pitch, tvl1_stats *stats) {
+                   size_t pitch1, int f32, int w, int h, int seeded, const float *u0,
+                   const float *v0, size_t init_pitch, float *u, float *v, size_t flow_pitch,
+                   tvl1_stats *stats) {
   if (!prm || !I0 || !I1 || !u || !v) return TVL1_EINVAL;
   if (w <= 0 || h <= 0) return TVL1_ESIZE;
+  if (seeded && (!u0 || !v0 || init_pitch < sizeof(float) * (size_t)w || init_pitch % 4 != 0 ||
+                 prm->profile == 1))
+    return TVL1_EINVAL;
   const size_t in_bytes = f32 ? sizeof(float) * (size_t)w : (size_t)w;
   if (pitch0 < in_bytes || pitch1 < in_bytes || flow_pitch < sizeof(float) * (size_t)w)
     return TVL1_EINVAL;
@@ -558,6 +564,28 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
   for (int s = 1; s < L; ++s) {
     resize_linear(lv[s - 1].I0, ws[s - 1], hs[s - 1], lv[s].I0, ws[s], hs[s], fdown, fdown, fma_mode);
     resize_linear(lv[s - 1].I1, ws[s - 1], hs[s - 1], lv[s].I1, ws[s], hs[s], fdown, fdown, fma_mode);
+  }
+
+  /* [A.2b] useInitialFlow: level 0 of the flow pyramid is the seed; each coarser level is
+   * the resize of the (rounded) level before with the image pyramid's step, then
+   * cuda::multiply(float(scaleStep)) as a rounding of its own (never fused into the resize:
+   * it is another kernel upstream).  Only the coarsest level is read: the solve overwrites
+   * the others on its way up.  u3 starts at zero. */
+  if (seeded) {
+    for (int y = 0; y < h; ++y) {
+      memcpy(lv[0].u1 + (size_t)y * w, (const char *)u0 + (size_t)y * init_pitch, sizeof(float) * w);
+      memcpy(lv[0].u2 + (size_t)y * w, (const char *)v0 + (size_t)y * init_pitch, sizeof(float) * w);
+    }
+    const float fmul = (float)prm->scale_step;
+    for (int s = 1; s < L; ++s) {
+      resize_linear(lv[s - 1].u1, ws[s - 1], hs[s - 1], lv[s].u1, ws[s], hs[s], fdown, fdown, fma_mode);
+      resize_linear(lv[s - 1].u2, ws[s - 1], hs[s - 1], lv[s].u2, ws[s], hs[s], fdown, fdown, fma_mode);
+      const size_t Ns = (size_t)ws[s] * hs[s];
+      for (size_t i = 0; i < Ns; ++i) {
+        lv[s].u1[i] = lv[s].u1[i] * fmul;
+        lv[s].u2[i] = lv[s].u2[i] * fmul;
+      }
+    }
   }
 
   const float l_t = (float)(prm->lambda * prm->theta);
@@ -664,12 +692,22 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
 int orc_tvl1_calc(const tvl1_params *prm, const uint8_t *I0, size_t pitch0,
                   const uint8_t *I1, size_t pitch1, int w, int h, float *u, float *v,
                   size_t flow_pitch, tvl1_stats *stats) {
-  return calc_in(prm, I0, pitch0, I1, pitch1, 0, w, h, u, v, flow_pitch, stats);
+  return calc_in(prm, I0, pitch0, I1, pitch1, 0, w, h, 0, NULL, NULL, 0, u, v, flow_pitch, stats);
+}
+
+/* tvl1_calc_host_init's contract (include/tvl1.h): the solve from the seed (u0, v0);
+ * TVL1_EINVAL for a null seed, a bad init_pitch or profile = 1 */
+int orc_tvl1_calc_init(const tvl1_params *prm, const uint8_t *I0, size_t pitch0,
+                       const uint8_t *I1, size_t pitch1, int w, int h, const float *u0,
+                       const float *v0, size_t init_pitch, float *u, float *v,
+                       size_t flow_pitch, tvl1_stats *stats) {
+  return calc_in(prm, I0, pitch0, I1, pitch1, 0, w, h, 1, u0, v0, init_pitch, u, v, flow_pitch,
+                 stats);
 }
 
 /* tvl1_calc_f32 on host buffers (pitches in bytes) */
 int orc_tvl1_calc_f32(const tvl1_params *prm, const float *I0, size_t pitch0, const float *I1,
                       size_t pitch1, int w, int h, float *u, float *v, size_t flow_pitch,
                       tvl1_stats *stats) {
-  return calc_in(prm, I0, pitch0, I1, pitch1, 1, w, h, u, v, flow_pitch, stats);
+  return calc_in(prm, I0, pitch0, I1, pitch1, 1, w, h, 0, NULL, NULL, 0, u, v, flow_pitch, stats);
 }

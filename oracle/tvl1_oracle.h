@@ -91,6 +91,14 @@ int orc_tvl1_calc_f32(const tvl1_params *params, const float *I0, size_t pitch0,
                       const float *I1, size_t pitch1, int w, int h, float *u, float *v,
                       size_t flow_pitch, tvl1_stats *stats);
 
+/* ... and tvl1_calc_host_init's: the solve from the seed (u0, v0), row pitch init_pitch bytes
+ * (SURVEY A.2b), in IEEE or, with fast_math = 2, in the contracted arithmetic; TVL1_EINVAL for
+ * a null seed, a bad init_pitch or profile = 1 */
+int orc_tvl1_calc_init(const tvl1_params *params, const uint8_t *I0, size_t pitch0,
+                       const uint8_t *I1, size_t pitch1, int w, int h, const float *u0,
+                       const float *v0, size_t init_pitch, float *u, float *v,
+                       size_t flow_pitch, tvl1_stats *stats);
+
 /* solve_wrapper post-ops (optflow.cpp:445-473) on host buffers */
 void orc_postprocess(float *u, float *v, size_t flow_pitch, const uint8_t *I1, size_t pitch1,
                      int w, int h, int mode);

@@ -8,7 +8,11 @@ calc_in -- the median before each warp, calcError = eps > 0 && (n & 1) && prevEr
 scaledEps, prevError -= scaledEps, the upsample with upmul.  test_initflow_ref_cpu.py pins the
 composition against checker.oracle_calc (bitwise, zero seed) before anything trusts it.
 
-The stage functions are IEEE only: fast_math 1 and 2 have no seeded reference.
+The stage functions are IEEE only.  The oracle has since grown a seeded whole-solve entry of its
+own (orc_tvl1_calc_init, checker.oracle_calc(init=...)) in both of its arithmetics:
+test_initflow_ref_cpu.py holds it to this composition bit for bit in IEEE, and it is the
+reference of the seeded solves in fma mode (fast_math 2, reference(..., math=2) below).
+fast_math 1 has no seeded reference.
 
 Also here: the deterministic seeds and the one table of (case, seed) pairs the GPU tests use,
 so the CPU suite can hold every one of them to the project's residual margin."""
@@ -241,11 +245,18 @@ def batch_pair(case, b):
 _ref_cache = {}
 
 
-def reference(key, I0, I1, params_kw, u0, v0):
-    """seeded_calc, computed once per key and shared (the results are never written to)."""
-    if key not in _ref_cache:
-        r = seeded_calc(I0, I1, capi.make_params(**params_kw), u0, v0)
+def reference(key, I0, I1, params_kw, u0, v0, math=0):
+    """(u, v, warp_iters, trace) of the seeded solve, computed once per key and arithmetic and
+    shared (the results are never written to): math 0 seeded_calc, math 2 the oracle's own
+    seeded entry in fma mode."""
+    if (key, math) not in _ref_cache:
+        if math == 0:
+            r = seeded_calc(I0, I1, capi.make_params(**params_kw), u0, v0)
+        else:
+            u, v, _, wi, tr = checker.oracle_check_trace(I0, I1, capi.make_params(fast_math=math, **params_kw),
+                                                         init=(u0, v0))
+            r = (u, v, wi, tr)
         for a in r:
             a.setflags(write=False)
-        _ref_cache[key] = r
-    return _ref_cache[key]
+        _ref_cache[(key, math)] = r
+    return _ref_cache[(key, math)]

@@ -1,6 +1,7 @@
 """tvl1_calc_batch_init: every pair of a seeded batch gets the seeded reference
-(tests/initflow_ref.py) bit for bit, whatever seeds the other pairs start from, through the
-on-chip coarsest level (kb_small_level<FM, true>), the streaming one and the per-pair path."""
+(tests/initflow_ref.py; in fma mode the oracle's own seeded entry) bit for bit, whatever seeds
+the other pairs start from, through the on-chip coarsest level (kb_small_level<FM, true>), the
+streaming one and the per-pair path."""
 import numpy as np
 import pytest
 
@@ -77,6 +78,24 @@ def test_seeded_batch_matches_the_composed_reference(built, monkeypatch, name, e
         assert bits_equal(u[b], ur) and bits_equal(v[b], vr), f"pair {b} not bit-exact"
 
 
+@pytest.mark.parametrize("env", ["", "TVL1_BATCH_SMALL=0", "TVL1_BATCH_FUSE=0"])
+@pytest.mark.parametrize("name", list(ref.BATCH))
+def test_seeded_batch_matches_the_oracle_in_fma(built, monkeypatch, name, env):
+    """fast_math 2: kb_flow_down<true>, kb_small_level<2, true> and the contracted streaming
+    kernels under per-pair seeds, bitwise against the oracle's seeded entry."""
+    set_env(monkeypatch, env)
+    case = ref.BATCH[name]
+    I0s, I1s, U0, V0 = batch_of(case)
+    eng = capi.Engine(capi.make_params(fast_math=2, **case["kw"]))
+    u, v, st = run_batch(eng, I0s, I1s, U0, V0)
+    eng.close()
+    for b in range(case["n"]):
+        ur, vr, wr, _ = ref.reference(("batch", name, b), I0s[b], I1s[b], case["kw"], U0[b], V0[b], math=2)
+        assert st[b]["levels"] == wr.shape[0]
+        np.testing.assert_array_equal(st[b]["warp_iters"], wr, err_msg=f"pair {b}")
+        assert bits_equal(u[b], ur) and bits_equal(v[b], vr), f"pair {b} not bit-exact"
+
+
 @pytest.mark.parametrize("name", list(ref.BATCH))
 def test_shared_seed_is_the_replicated_seed(built, name):
     """init_pair_stride = 0: one seed for every pair."""
@@ -94,11 +113,12 @@ def test_shared_seed_is_the_replicated_seed(built, name):
     assert bits_equal(a[0][k], ur) and bits_equal(a[1][k], vr)
 
 
-@pytest.mark.parametrize("math", [0, 2])
+@pytest.mark.parametrize("math", [0, 1, 2])
 @pytest.mark.parametrize("env", ["", "TVL1_BATCH_SMALL=0"])
 def test_seeded_batch_pair_is_the_single_seeded_solve(built, monkeypatch, math, env):
-    """fast_math 2 has no seeded reference: each pair of the batch must be tvl1_calc_init of
-    that pair alone, bitwise (IEEE too)."""
+    """Each pair of the batch must be tvl1_calc_init of that pair alone, bitwise.  fast_math 1
+    has no seeded reference: this equality is what holds its batched seed chain and on-chip
+    level.  IEEE and fma mode are also held to their references above."""
     set_env(monkeypatch, env)
     case = ref.BATCH["strip6"]
     I0s, I1s, U0, V0 = batch_of(case)
@@ -125,6 +145,20 @@ def test_gamma_batch_takes_the_seeded_single_path(built):
     eng.close()
 
 
+def test_gamma_batch_in_fma(built):
+    """fast_math 2 with gamma != 0: the engine and the oracle both solve in IEEE, seed chain
+    included; each pair bitwise the oracle's seeded entry."""
+    case = ref.BATCH_GAMMA
+    I0s, I1s, U0, V0 = batch_of(case)
+    eng = capi.Engine(capi.make_params(fast_math=2, **case["kw"]))
+    u, v, st = run_batch(eng, I0s, I1s, U0, V0)
+    eng.close()
+    for b in range(case["n"]):
+        ur, vr, wr, _ = ref.reference(("batch_gamma", b), I0s[b], I1s[b], case["kw"], U0[b], V0[b], math=2)
+        np.testing.assert_array_equal(st[b]["warp_iters"], wr)
+        assert bits_equal(u[b], ur) and bits_equal(v[b], vr)
+
+
 @pytest.mark.parametrize("name", ["one_level_pitched", "one_level_chip"])
 def test_one_level_batch_copies_the_seed(built, name):
     """nscales 1: the seed is the coarsest level as it is (kb_flow_copy); 50 x 30 streams,
@@ -141,3 +175,18 @@ def test_one_level_batch_copies_the_seed(built, name):
     assert bits_equal(u[1], ur) and bits_equal(v[1], vr)
     np.testing.assert_array_equal(st[1]["warp_iters"], wr)
     assert bits_equal(u[0], u[2]) and not bits_equal(u[0], u[1])
+
+
+@pytest.mark.parametrize("name", ["one_level_pitched", "one_level_chip"])
+def test_one_level_batch_copies_the_seed_in_fma(built, name):
+    c = ref.SINGLE[name]
+    I0, I1 = ref.frames_of(c)
+    u0, v0 = ref.seed_of(c)
+    z = np.zeros_like(u0)
+    ur, vr, wr, _ = ref.reference(("single", name), I0, I1, c["kw"], u0, v0, math=2)
+    eng = capi.Engine(capi.make_params(fast_math=2, **c["kw"]))
+    u, v, st = run_batch(eng, np.stack([I0, I0, I0]), np.stack([I1, I1, I1]), np.stack([z, u0, z]),
+                         np.stack([z, v0, z]))
+    eng.close()
+    assert bits_equal(u[1], ur) and bits_equal(v[1], vr)
+    np.testing.assert_array_equal(st[1]["warp_iters"], wr)

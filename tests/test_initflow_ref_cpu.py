@@ -4,6 +4,9 @@
     is zero -- the composition is pinned before it is trusted;
   * every (case, seed) pair of the GPU tests keeps its stopping decisions at least the
     project's MIN_MARGIN (tests/test_residual_margin_cpu.py) from the thresholds;
+  * the oracle's own seeded entry (orc_tvl1_calc_init, checker.oracle_calc(init=...)) equals
+    that composition bit for bit in IEEE on every GPU case, and the unseeded oracle under a
+    zero seed in IEEE and in fma -- it is the reference of the seeded fma-mode GPU tests;
   * the engine library exports the three entry points and rejects bad seed arguments before
     anything touches a device;
   * the CLI's `initialFlow` key: inert without `useInitialFlow`, an error with `features`."""
@@ -66,6 +69,10 @@ def test_seed_pyramid_is_a_chain_of_rounded_levels(built):
     np.testing.assert_allclose(c[3][1], -11 * 0.8 ** 3, rtol=1e-6)
 
 
+def oracle_seeded_trace(I0, I1, p, u0, v0):
+    return checker.oracle_check_trace(I0, I1, p, init=(u0, v0))
+
+
 def _gpu_cases():
     out = []
     for name, c in ref.SINGLE.items():
@@ -82,6 +89,60 @@ def test_gpu_cases_clear_the_residual_margin(built, make):
     (I0, I1), (u0, v0), kw = make()
     p = capi.make_params(**kw)
     _, _, wi, trace = ref.seeded_calc(I0, I1, p, u0, v0)
+    if p.epsilon == 0:
+        assert len(trace) == 0
+        return
+    m = checker.check_margins(trace, p.iterations)
+    assert m.min() >= MIN_MARGIN, trace[np.argmin(m)]
+
+
+@pytest.mark.parametrize("make", _gpu_cases())
+def test_oracle_seeded_entry_is_the_composition(built, make):
+    """IEEE: flow bits and per-warp counts of orc_tvl1_calc_init == seeded_calc."""
+    (I0, I1), (u0, v0), kw = make()
+    p = capi.make_params(**kw)
+    ur, vr, wr, _ = ref.seeded_calc(I0, I1, p, u0, v0)
+    u, v, st, wi = checker.oracle_calc(I0, I1, p, init=(u0, v0))
+    assert st["levels"] == wr.shape[0]
+    np.testing.assert_array_equal(wi, wr)
+    assert bits_equal(u, ur) and bits_equal(v, vr)
+
+
+@pytest.mark.parametrize("math", [0, 2], ids=["ieee", "fma"])
+@pytest.mark.parametrize("w,h,kw", [
+    (97, 40, dict(nscales=3, warps=3)),
+    (97, 61, dict(gamma=0.1)),
+    (96, 64, dict(median_filtering=5)),
+    (200, 60, dict(nscales=4, warps=3, epsilon=0.0, iterations=7)),
+    (40, 24, dict(nscales=5)),
+], ids=["97x40_s3w3", "gamma", "median5", "fixed_work", "40x24_break"])
+def test_oracle_zero_seed_is_the_unseeded_oracle(built, w, h, kw, math):
+    p = capi.make_params(fast_math=math, **kw)
+    I0, I1 = synth.gen_pair(w, h, seed=w * 7 + h)
+    ur, vr, sr, wr = checker.oracle_calc(I0, I1, p)
+    z = np.zeros((h, w), np.float32)
+    u, v, st, wi = checker.oracle_calc(I0, I1, p, init=(z, z))
+    assert st == sr
+    np.testing.assert_array_equal(wi, wr)
+    assert bits_equal(u, ur) and bits_equal(v, vr)
+
+
+def test_oracle_seeded_entry_rejects_what_the_engine_rejects(built):
+    I0, I1 = synth.gen_pair(40, 24, seed=3)
+    z = np.zeros((24, 40), np.float32)
+    with pytest.raises(capi.TVL1Error, match="TVL1_EINVAL"):
+        checker.oracle_calc(I0, I1, capi.make_params(profile=1, nscales=2), init=(z, z))
+    with pytest.raises(ValueError):
+        checker.oracle_calc(I0, I1, capi.make_params(), init=(z[:, :39], z[:, :39]))
+
+
+@pytest.mark.parametrize("make", _gpu_cases())
+def test_gpu_cases_clear_the_residual_margin_in_fma(built, make):
+    """The fma-mode twin of the margin test above, on the oracle's own seeded entry (the
+    reference of the fma-mode GPU tests)."""
+    (I0, I1), (u0, v0), kw = make()
+    p = capi.make_params(fast_math=2, **kw)
+    *_, trace = oracle_seeded_trace(I0, I1, p, u0, v0)
     if p.epsilon == 0:
         assert len(trace) == 0
         return
