@@ -22,6 +22,7 @@
 
 #include "../../include/tvl1.h"
 #include "tvl1_plan.hpp"
+#include "tvl1_walk.hpp"
 #include "tvl1_kernels.hpp"
 #include "tvl1_batch.hpp"
 #include "tvl1_align.hpp"
@@ -934,18 +935,7 @@ static tvl1_status upsample(const Level &lv, int uset) {
   return TVL1_OK;
 }
 
-// One iteration pass: k iterations (ending in a check if calc_end) from the buffer sets
-// (ui, pi) into (ui ^ 1, pi ^ 1), with the constants of set cb.  gate: a speculative launch
-// (DESIGN 4.8), which runs only if *gate == gseq.
-struct Pass {
-  int k;
-  bool calc_end;
-  int ui, pi, cb;
-  bool p_zero;
-  const unsigned long long *gate;
-  unsigned long long gseq;
-};
-
+// (One iteration pass: PassReq, tvl1_walk.hpp.)
 // Each launcher takes the pass's IterArgs (planes and flags set), launches its kernel family
 // and returns the number of residual partials the pass wrote (-1: the ctx's error is set, a
 // TVL1_EHIP), with the compulsory HBM bytes of the launch in *hbm.
@@ -956,14 +946,14 @@ static int partials_fit(tvl1_ctx *c, int need, int blocks, const char *what) {
 }
 
 // the warp's first pass with warpBackward fused in (k_warp_iter), storing the constants if store_c
-static int launch_warp_iter(const Level &lv, const IterArgs &a, const Pass &p, bool store_c, double *hbm) {
+static int launch_warp_iter(const Level &lv, const IterArgs &a, const PassReq &p, double *hbm) {
   tvl1_ctx *c = lv.c;
   WarpIterArgs w;
   w.ra.b = roll_bufs(c, lv.s, p.ui, p.pi, p.cb);
   w.ra.it = a;
   w.I0 = c->I0s[lv.s];
   w.I1 = c->I1s[lv.s];
-  w.store_c = store_c ? 1 : 0;
+  w.store_c = p.store_c ? 1 : 0;
   constexpr int M = kWiMargin, BW = 128;
   const StreamPlan sp = plan_warp_iter(lv.lw, lv.lh, BW, M, fill_slots(c->witer_slots, fill_now(c)), c->roll_seg);
   w.ra.bands = sp.bands;
@@ -978,12 +968,12 @@ static int launch_warp_iter(const Level &lv, const IterArgs &a, const Pass &p, b
     hipLaunchKernelGGL((k_warp_iter<M, FM, BW, 1, 1>), dim3(w.ra.waves), dim3(64 + BW), 0, lv.st, w);
   MATH_SWITCH(lv.math, WITER)
 #undef WITER
-  *hbm = warp_iter_hbm(sp, lv.lh, BW, wi_ww<M, BW>(), (double)lv.lw * lv.lh, p.p_zero, store_c);
+  *hbm = warp_iter_hbm(sp, lv.lh, BW, wi_ww<M, BW>(), (double)lv.lw * lv.lh, p.p_zero, p.store_c);
   return sp.waves;
 }
 
 // taut < 0 or not finite: one iteration per launch, IEEE divisions (k_iterate)
-static int launch_iterate(const Level &lv, const IterArgs &a, const Pass &p, double *hbm) {
+static int launch_iterate(const Level &lv, const IterArgs &a, const PassReq &p, double *hbm) {
   const int nblk = iterate_blocks(lv.lw, lv.lh);
   if (lv.gam)
     hipLaunchKernelGGL((k_iterate<true, true>), dim3(nblk), dim3(kBlock), 0, lv.st, a);
@@ -993,9 +983,10 @@ static int launch_iterate(const Level &lv, const IterArgs &a, const Pass &p, dou
   return nblk;
 }
 
-// the streaming pass (k_iterate_roll<G, K, PX>); midp: a 4-iteration pass that also keeps the
+// the streaming pass (k_iterate_roll<G, K, PX>); p.mid: a 4-iteration pass that also keeps the
 // residual after 2 (k_iterate_roll_mid: two partials per wavefront)
-static int launch_roll(const Level &lv, const IterArgs &a, const Pass &p, bool midp, double *hbm) {
+static int launch_roll(const Level &lv, const IterArgs &a, const PassReq &p, double *hbm) {
+  const bool midp = p.mid;
   tvl1_ctx *c = lv.c;
   hipStream_t st = lv.st;
   const int k = p.k, math = lv.math;
@@ -1058,7 +1049,7 @@ static int launch_roll(const Level &lv, const IterArgs &a, const Pass &p, bool m
 }
 
 // blocked pass in 64 x 48 regions, 3 rows x 2 px per thread (k_iterate_tb4, gamma = 0)
-static int launch_tb4(const Level &lv, const IterArgs &a, const Pass &p, double *hbm) {
+static int launch_tb4(const Level &lv, const IterArgs &a, const PassReq &p, double *hbm) {
   const BlockedPlan bp = tb4_plan(lv.lw, lv.lh, p.k);
   TBArgs t;
   t.it = a;
@@ -1077,7 +1068,7 @@ static int launch_tb4(const Level &lv, const IterArgs &a, const Pass &p, double 
 }
 
 // blocked pass in 64 x 32 regions, 2 px per lane (k_iterate_tb)
-static int launch_tb(const Level &lv, const IterArgs &a, const Pass &p, double *hbm) {
+static int launch_tb(const Level &lv, const IterArgs &a, const PassReq &p, double *hbm) {
   const BlockedPlan bp = tb_plan(lv.lw, lv.lh, p.k);
   TBArgs t;
   t.it = a;
@@ -1106,27 +1097,26 @@ static int launch_tb(const Level &lv, const IterArgs &a, const Pass &p, double *
 // while the level has enough rows for one round of >= 32-row segments (short segments
 // repeat the 2K-row halo) and k_iterate_tb (64 x 32 regions, 2 px/lane) wins below.
 // Planes beyond 32-bit buffer offsets take k_iterate_tb for every pass.
-// witer: the warp's first pass as k_warp_iter (storing the constants if store_c); midp: a
+// p.witer: the warp's first pass as k_warp_iter (storing the constants if p.store_c); p.mid: a
 // mid-check pass.  blocks_out: the residual partials of the pass (per check of a mid pass).
-static tvl1_status launch_pass(const Level &lv, const Pass &p, int wp, int n, int &blocks_out,
-                               bool witer = false, bool store_c = false, bool midp = false) {
+static tvl1_status launch_pass(const Level &lv, const PassReq &p, int wp, int n, int &blocks_out) {
   tvl1_ctx *c = lv.c;
   IterArgs a = lv.a;
   set_planes(c, a, p.ui, p.pi, p.cb);
   a.calc_err = p.calc_end ? 1 : 0;
   a.p_zero = p.p_zero ? 1 : 0;
-  a.gate = p.gate;
+  a.gate = p.gated ? c->gate : nullptr;
   a.gate_seq = p.gseq;
   const size_t tkp = prof_begin(c, lv.st);
   const double Nl = (double)lv.lw * lv.lh;
   double hbm = 0.0;
   int blocks;
-  if (witer)
-    blocks = launch_warp_iter(lv, a, p, store_c, &hbm);
+  if (p.witer)
+    blocks = launch_warp_iter(lv, a, p, &hbm);
   else if (lv.exact_div)
     blocks = launch_iterate(lv, a, p, &hbm);
   else if (lv.roll_ok && (p.k <= 2 || lv.roll_long))
-    blocks = launch_roll(lv, a, p, midp, &hbm);
+    blocks = launch_roll(lv, a, p, &hbm);
   else if (c->tb4 && !lv.gam)
     blocks = launch_tb4(lv, a, p, &hbm);
   else
@@ -1134,34 +1124,72 @@ static tvl1_status launch_pass(const Level &lv, const Pass &p, int wp, int n, in
   if (blocks < 0) return TVL1_EHIP;
   // algorithmic: 64 B/px per executed iteration (+ 40 B/px for a fused
   // warpBackward)
-  prof_end(c, lv.st, tkp, 0, Nl * 64.0 * p.k + (witer ? Nl * 40.0 : 0.0), hbm);
+  prof_end(c, lv.st, tkp, 0, Nl * 64.0 * p.k + (p.witer ? Nl * 40.0 : 0.0), hbm);
   DIAG(c, lv.st, "iteration pass", lv.s, wp, n);
   blocks_out = blocks;
   return TVL1_OK;
 }
 
-// the speculation gate of a check at iteration count n: gated itself on the check gin_seq (a
-// check enqueued behind another), and evaluating the prediction (pk, pcalc) for the launch
-// enqueued behind it
-static CheckGate check_gate(const tvl1_ctx *c, const Predictor &pr, int n, int pk, int pcalc,
-                            unsigned long long gin_seq, bool gated) {
-  CheckGate gt{};
-  if (gated) {
-    gt.in = c->gate;
-    gt.in_seq = gin_seq;
+// walk_level's backend (tvl1_walk.hpp): the launches of one level of a single-pair solve
+struct LevelOps {
+  const Level &lv;
+  const WalkLevel &wl;
+  tvl1_stats *stats;
+  // profiling marks and check numbers taken so far: launches that ran empty give theirs back
+  struct Mark {
+    size_t marks, ev_used;
+    unsigned long long check_seq;
+  };
+
+  // build-only median of u before a warp
+  tvl1_status median(int ui) {
+    tvl1_ctx *c = lv.c;
+    hipLaunchKernelGGL(k_median, grid2(lv.lw, lv.lh, 2), kBlk2, 0, lv.st, c->U[ui][0], c->U[ui][1], lv.lw,
+                       lv.lh, lv.P, c->prm.median_filtering, c->U[ui ^ 1][0], c->U[ui ^ 1][1]);
+    if (lv.gam) {
+      const size_t n = (size_t)lv.P * lv.lh * sizeof(float);
+      HIP_TRY(c, hipMemcpyAsync(c->U[ui ^ 1][2], c->U[ui][2], n, hipMemcpyDeviceToDevice, lv.st));
+    }
+    return TVL1_OK;
   }
-  if (pk >= 0) {
-    gt.out = c->gate;
-    gt.thr = pr.scaledEps;
-    gt.n = n;
-    gt.iters = pr.iterations;
-    gt.kmax = pr.kmax;
-    gt.eps_pos = 1;
-    gt.pk = pk;
-    gt.pcalc = pcalc;
+  tvl1_status gather(int ui, int cb, int wp) { return ::gather(lv, ui, cb, wp); }
+  tvl1_status pass(const PassReq &p, int wp, int n, int *blocks) { return launch_pass(lv, p, wp, n, *blocks); }
+  // the check's speculation gate: the device word, and the level's stopping rule for gate_holds
+  tvl1_status check(const CheckReq &q, unsigned long long *seq) {
+    CheckGate gt{};
+    if (q.gated_in) {
+      gt.in = lv.c->gate;
+      gt.in_seq = q.in_seq;
+    }
+    if (q.gate_out) {
+      gt.out = lv.c->gate;
+      gt.thr = wl.scaledEps;
+      gt.n = q.n;
+      gt.iters = wl.iterations;
+      gt.kmax = wl.kmax;
+      gt.eps_pos = 1;
+      gt.pk = q.pk;
+      gt.pcalc = q.pcalc;
+    }
+    return launch_check(lv.c, lv.st, q.blocks, gt, seq, q.first);
   }
-  return gt;
-}
+  tvl1_status wait(unsigned long long seq, double *e) { return wait_check(lv.c, lv.st, seq, e); }
+  Mark mark() const { return Mark{lv.c->marks.size(), lv.c->ev_used, lv.c->check_seq}; }
+  void rollback(const Mark &m) {
+    lv.c->marks.resize(m.marks);
+    lv.c->ev_used = m.ev_used;
+    lv.c->check_seq = m.check_seq;
+  }
+  // speculates only a solve alone on its device (TVL1_SPEC=2: always)
+  bool alone() const {
+    return !(lv.c->spec == 1 && g_solving[lv.c->device & 63].load(std::memory_order_relaxed) > 1);
+  }
+  void trace(const char *line) { fputs(line, stderr); }
+  void warp_done(int wp, int n) {
+    const int i = lv.s * wl.warps + wp;
+    if (stats && stats->warp_iterations && i < stats->warp_iterations_capacity) stats->warp_iterations[i] = n;
+  }
+};
 
 // [A.1] convertTo + [A.2] pyramid, kernel step = float(1/scaleStep)
 static tvl1_status build_pyramid(tvl1_ctx *c, const Frames &in, int W, int H, hipStream_t st) {
@@ -1257,9 +1285,8 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
   }
 
   TVL1_TRY(build_pyramid(c, in, W, H, st));
-  int ui = 0, pi = 0;  // ping-pong indices of the u and p buffer sets
-  int cb = 0;          // constants buffer (I1wx, I1wy, rho) of the current warp
-  TVL1_TRY(initial_flow(c, seed, W, H, st, &ui));
+  WalkState ws{0, 0, 0, 50.0};   // the buffer sets in use (u, p, constants), and w0_hint
+  TVL1_TRY(initial_flow(c, seed, W, H, st, &ws.ui));
 
   const float taut = (float)(prm.tau / prm.theta);
   // The projection's shared-reciprocal division (dual_px) needs ng = 1 + taut*|grad u| >= 1;
@@ -1267,20 +1294,10 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
   const bool exact_div = !(taut >= 0.0f && taut <= FLT_MAX);
 
   int64_t level_iters[TVL1_MAX_LEVELS] = {};
-  int64_t checks = 0;
-  int32_t spec_misses = 0;   // speculative launches that ran empty
-  int mid_passes = 0, mid_taken = 0;   // mid-check passes; of those, ended on the mid state
-  // speculates only a solve alone on its device (TVL1_SPEC=2: always)
-  auto alone = [&]() {
-    return !(c->spec == 1 && g_solving[c->device & 63].load(std::memory_order_relaxed) > 1);
-  };
-
-  double w0_hint = 50.0;   // speculation: residual / (eps^2 W H) at a level's first check
+  WalkCounts ct;
   for (int s = L - 1; s >= 0; --s) {
     const int lw = g.ws[s], lh = g.hs[s], P = g.ps[s];
     const double scaledEps = prm.epsilon * prm.epsilon * (double)lw * (double)lh;
-    bool p_zero = true;  // p = 0 at the start of every level (setTo(0) in procOneScale)
-
     Level lv{};
     lv.c = c;
     lv.st = st;
@@ -1298,251 +1315,48 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
     lv.roll_long = lv.roll_ok && (long)((lw + 55) / 56) * ((lh + 31) / 32) >= c->roll_long_min;
     const bool roll_ok = lv.roll_ok;
 
+    WalkLevel wl{};
+    wl.level = s;
+    wl.warps = prm.warps;
+    wl.iterations = prm.iterations;
+    wl.kmax = exact_div ? 1 : roll_ok ? kRollMax : kTbMax;
+    wl.scaledEps = scaledEps;
+    wl.eps_pos = prm.epsilon > 0;
     // warpBackward fused into the warp's first pass (2 iterations ending in the first
     // check) when that pass would stream through k_iterate_roll anyway
-    const bool fuse = c->fuse && !gam && !exact_div && roll_ok && prm.epsilon > 0 &&
-                      prm.iterations >= 2 && (long)lw * lh >= c->fuse_min;
-    const int kmax = exact_div ? 1 : roll_ok ? kRollMax : kTbMax;
-    // the mid-check pass (k_iterate_roll_mid) where a 4-iteration pass streams
-    const bool mid_ok = !gam && !exact_div && lv.roll_long && prm.epsilon > 0 && kRollMax >= 4;
+    wl.fuse = c->fuse && !gam && !exact_div && roll_ok && prm.epsilon > 0 && prm.iterations >= 2 &&
+              (long)lw * lh >= c->fuse_min;
+    wl.median = median;
     // Speculation: behind each residual check the host enqueues the launch it
     // expects to follow, gated on the device by the check's own evaluation of the stopping
     // rule, and only then waits for the residual.  A right guess hides the host round trip;
     // a wrong one costs an empty launch, and the host enqueues the right work as before.
-    const bool spec_ok = c->spec && !exact_div && roll_ok && prm.epsilon > 0;
-    const bool spec_stop_ok = spec_ok && !median && prm.iterations >= 2;
-    Predictor pred(prm.iterations, kmax, scaledEps, prm.warps, spec_ok, spec_stop_ok,
-                   c->mid && mid_ok, w0_hint);
-    using Hist = Predictor::Hist;
-
-    int last_warp_n = -1;   // iterations of the level's previous warp
-    // a warp whose first pass (and check) the previous warp enqueued speculatively
-    bool pre = false;
-    bool pre_nostore = false;
-    unsigned long long pre_seq = 0;
-    int pre_pk = -1, pre_pcalc = 0;
-    for (int wp = 0; wp < prm.warps; ++wp) {
-      bool fused_nostore = false;   // k_warp_iter ran without storing the constants
-      double error = DBL_MAX;
-      double prevError = 0.0;
-      int n = 0;
-      // a check enqueued but not yet read: its sequence number and prediction
-      bool pending = false;
-      unsigned long long pend_seq = 0;
-      int pend_pk = -1, pend_pcalc = 0;
-      Hist h;
-      if (pre) {
-        n = 2;
-        fused_nostore = pre_nostore;
-        pending = true;
-        pend_seq = pre_seq;
-        pend_pk = pre_pk;
-        pend_pcalc = pre_pcalc;
-        pre = false;
-      } else {
-        if (median) {
-          hipLaunchKernelGGL(k_median, grid2(lw, lh, 2), kBlk2, 0, st, c->U[ui][0], c->U[ui][1],
-                             lw, lh, P, prm.median_filtering, c->U[ui ^ 1][0], c->U[ui ^ 1][1]);
-          if (gam) {
-            const size_t n = (size_t)P * lh * sizeof(float);
-            HIP_TRY(c, hipMemcpyAsync(c->U[ui ^ 1][2], c->U[ui][2], n, hipMemcpyDeviceToDevice, st));
-          }
-          ui ^= 1;
-        }
-        if (!fuse) TVL1_TRY(gather(lv, ui, cb, wp));
-      }
-      bool next_pre = false;   // this warp stopped where predicted: the next warp has begun
-      while (pending || (error > scaledEps && n < prm.iterations)) {
-        if (!pending) {
-          bool calc_end = false;
-          double prev_sim = prevError;
-          const int k = sched_after(prevError, scaledEps, n, prm.iterations, kmax,
-                                    prm.epsilon > 0, &calc_end, &prev_sim);
-          // A converging warp (a check every second iteration, the error just above eps^2 W H)
-          // runs its next two 2-iteration passes as one k_iterate_roll_mid pass: both checks'
-          // residuals and the state after 4 iterations in the usual set.  The host reads the
-          // first check as procOneScale does; if the warp stops there (or its schedule is not
-          // a second 2-iteration pass) a 2-iteration pass from the same input set, which the
-          // mid-check pass leaves as it was, recomputes the state at that check (DESIGN.md
-          // §4.1 of r6).  Not for a warp's first check (n = 2: its error drops the
-          // most), nor where the 4-iteration pass does not stream.
-          if (c->mid && mid_ok && k == 2 && calc_end && n > 2 && n + 4 <= prm.iterations &&
-              prevError >= c->mid_min * scaledEps) {
-            int blocks = 0;
-            TVL1_TRY(launch_pass(lv, Pass{4, true, ui, pi, cb, p_zero, nullptr, 0}, wp, n, blocks, false,
-                                 false, true));
-            unsigned long long seq_mid = 0, seq_end = 0;
-            TVL1_TRY(launch_check(c, st, blocks, CheckGate{}, &seq_mid, blocks));
-            TVL1_TRY(launch_check(c, st, blocks, CheckGate{}, &seq_end));
-            double e_mid = 0.0;
-            TVL1_TRY(wait_check(c, st, seq_mid, &e_mid));
-            n += 2;
-            ++checks;
-            pred.note(h, e_mid, n);
-            ++mid_passes;
-            bool ce2 = false;
-            double prev2 = 0.0;
-            const bool stop = !(e_mid > scaledEps && n < prm.iterations);
-            if (!stop &&
-                sched_after(e_mid, scaledEps, n, prm.iterations, kmax, 1, &ce2, &prev2) == 2 && ce2) {
-              double e_end = 0.0;   // the second check: the next pass's own
-              TVL1_TRY(wait_check(c, st, seq_end, &e_end));
-              n += 2;
-              ++checks;
-              pred.note(h, e_end, n);
-              error = e_end;
-              prevError = e_end;
-            } else {   // the state at the first check: its 2 iterations again, no residual
-              ++mid_taken;
-              TVL1_TRY(launch_pass(lv, Pass{2, false, ui, pi, cb, false, nullptr, 0}, wp, n - 2, blocks));
-              error = e_mid;
-              prevError = e_mid;
-            }
-            p_zero = false;
-            ui ^= 1;
-            pi ^= 1;
-            continue;
-          }
-          const bool witer = fuse && n == 0 && k == 2 && calc_end;
-          // the constants go to HBM only when the warp may run further passes: always for
-          // a level's first warp, else when the previous warp did not stop at its first
-          // check (a wrong guess recomputes them with the warp kernel after the check)
-          const bool store_c = wp == 0 || last_warp_n != 2;
-          int blocks = 0;
-          TVL1_TRY(launch_pass(lv, Pass{k, calc_end, ui, pi, cb, p_zero, nullptr, 0}, wp, n, blocks, witer,
-                               store_c));
-          if (witer) fused_nostore = !store_c;
-          p_zero = false;
-          ui ^= 1;
-          pi ^= 1;
-          n += k;
-          if (!calc_end) {
-            error = DBL_MAX;
-            prevError = prev_sim;
-            continue;
-          }
-          pred.predict(wp, n, alone(), fused_nostore, last_warp_n, h, false, pend_pk, pend_pcalc);
-          TVL1_TRY(launch_check(c, st, blocks, check_gate(c, pred, n, pend_pk, pend_pcalc, 0, false),
-                                &pend_seq));
-        }
-        pending = false;
-        // the predicted launch(es) behind the check, gated on it
-        const int sp_pk = pend_pk, sp_pcalc = pend_pcalc;
-        const size_t marks0 = c->marks.size(), ev0 = c->ev_used;
-        const unsigned long long seq0 = c->check_seq;
-        unsigned long long sp_seq = 0;   // the speculative launch's own check
-        int sp_pk2 = -1, sp_pcalc2 = 0;
-        bool sp_nostore = false;
-        if (sp_pk == 0) {   // the next warp's first pass and check
-          const int w2 = wp + 1, cb2 = cb ^ 1;
-          const bool store2 = n != 2;   // k_warp_iter's store rule, if this warp stops here
-          int blocks = 0;
-          // the gather is not gated (a gate check costs k_warp_ring 34 VGPRs): after a wrong
-          // guess it has only filled the constants set the next warp recomputes anyway
-          if (!fuse) TVL1_TRY(gather(lv, ui, cb2, w2));
-          TVL1_TRY(launch_pass(lv, Pass{2, true, ui, pi, cb2, false, c->gate, pend_seq}, w2, 0, blocks, fuse,
-                               store2));
-          sp_nostore = fuse && !store2;
-          pred.note_stop_guess(n);   // (as guessed; recorded after the read)
-          pred.predict(w2, 2, alone(), sp_nostore, n, Hist{}, true, sp_pk2, sp_pcalc2);
-          TVL1_TRY(launch_check(c, st, blocks, check_gate(c, pred, 2, sp_pk2, sp_pcalc2, pend_seq, true),
-                                &sp_seq));
-        } else if (sp_pk > 0) {   // this warp's next pass
-          int blocks = 0;
-          TVL1_TRY(launch_pass(lv, Pass{sp_pk, sp_pcalc != 0, ui, pi, cb, false, c->gate, pend_seq}, wp, n,
-                               blocks));
-          if (sp_pcalc) {
-            Hist h2;   // with check j's residual extrapolated
-            h2.r0 = h.r1;
-            h2.n0 = h.n_last;
-            h2.r1 = h.r1 < 0 ? -1.0 : pred.extrapolate(h, n, wp);
-            h2.n_last = n;
-            pred.predict(wp, n + sp_pk, alone(), false, last_warp_n, h2, false, sp_pk2, sp_pcalc2);
-            TVL1_TRY(launch_check(c, st, blocks,
-                                  check_gate(c, pred, n + sp_pk, sp_pk2, sp_pcalc2, pend_seq, true), &sp_seq));
-          }
-        }
-        TVL1_TRY(wait_check(c, st, pend_seq, &error));   // the cuda::sum -> host read
-        prevError = error;
-        ++checks;
-        const bool ends = !(error > scaledEps && n < prm.iterations);
-        if (wp == 0 && h.r1 < 0) w0_hint = pred.w0_hint = error / scaledEps;
-        pred.note(h, error, n);
-        bool right = false;
-        double sp_prev = 0.0;
-        if (sp_pk == 0) {
-          right = ends;
-        } else if (sp_pk > 0 && !ends) {
-          bool ce;
-          right = sched_after(error, scaledEps, n, prm.iterations, kmax, 1, &ce, &sp_prev) == sp_pk &&
-                  (int)ce == sp_pcalc;
-        }
-        if (c->spec_trace)
-          fprintf(stderr, "spec level %d warp %d n %d E/thr %.3f guess %d/%d %s\n", s, wp, n,
-                  error / scaledEps, sp_pk, sp_pcalc, sp_pk < 0 ? "-" : right ? "hit" : "miss");
-        if (sp_pk >= 0 && !right) {   // the gated launches ran empty: forget them
-          ++spec_misses;
-          c->marks.resize(marks0);
-          c->ev_used = ev0;
-          c->check_seq = seq0;
-        }
-        if (right && sp_pk == 0) {   // the next warp's first pass is done, its check pending
-          ui ^= 1;
-          pi ^= 1;
-          p_zero = false;
-          next_pre = true;
-          pre_nostore = sp_nostore;
-          pre_seq = sp_seq;
-          pre_pk = sp_pk2;
-          pre_pcalc = sp_pcalc2;
-          break;
-        }
-        if (right) {   // the warp's next pass is done
-          p_zero = false;
-          ui ^= 1;
-          pi ^= 1;
-          n += sp_pk;
-          if (sp_pcalc) {
-            pending = true;
-            pend_seq = sp_seq;
-            pend_pk = sp_pk2;
-            pend_pcalc = sp_pcalc2;
-          } else {
-            error = DBL_MAX;
-            prevError = sp_prev;
-          }
-          continue;
-        }
-        // k_warp_iter guessed that this warp stops here; it continues: compute its
-        // constants (from its input u, the set the pass just read) before the next pass
-        if (fused_nostore && !ends) TVL1_TRY(gather(lv, ui ^ 1, cb, wp));
-        fused_nostore = false;
-      }
-      level_iters[s] += n;
-      last_warp_n = n;
-      if (stats && stats->warp_iterations && s * prm.warps + wp < stats->warp_iterations_capacity)
-        stats->warp_iterations[s * prm.warps + wp] = n;
-      cb ^= 1;  // every warp gets the other constants buffer
-      pre = next_pre;
-      pred.next_warp();
-    }
+    wl.spec = c->spec && !exact_div && roll_ok && prm.epsilon > 0;
+    // the mid-check pass (k_iterate_roll_mid) where a 4-iteration pass streams
+    wl.mid = c->mid && !gam && !exact_div && lv.roll_long && prm.epsilon > 0 && kRollMax >= 4;
+    wl.mid_min = c->mid_min;
+    wl.spec_trace = c->spec_trace != 0;
+    LevelOps ops{lv, wl, stats};
+    ct.level_iters = 0;
+    TVL1_TRY(walk_level(ops, wl, ws, ct));
+    level_iters[s] = ct.level_iters;
     HIP_TRY(c, hipGetLastError());
     if (s == 0) break;
-    TVL1_TRY(upsample(lv, ui));  // zoom the flow to level s-1, scale by 1/scaleStep
-    ui ^= 1;
+    TVL1_TRY(upsample(lv, ws.ui));  // zoom the flow to level s-1, scale by 1/scaleStep
+    ws.ui ^= 1;
   }
   const size_t tk = prof_begin(c, st);
-  hipLaunchKernelGGL(k_output, grid2(W, H), kBlk2, 0, st, c->U[ui][0], c->U[ui][1], W, H,
+  hipLaunchKernelGGL(k_output, grid2(W, H), kBlk2, 0, st, c->U[ws.ui][0], c->U[ws.ui][1], W, H,
                      g.ps[0], u, v, fpitch);
   prof_end(c, st, tk, 2, (double)W * H * 16.0);
   HIP_TRY(c, hipGetLastError());
 
   ClassTotals tot;
-  if (stats) fill_stats(stats, g, prm.warps, level_iters, checks, spec_misses);
+  if (stats) fill_stats(stats, g, prm.warps, level_iters, ct.checks, ct.spec_misses);
   TVL1_TRY(sum_marks(c, tot));
   if (stats) put_class_totals(stats, tot);
-  if (c->spec_trace && mid_passes)
-    fprintf(stderr, "mid-check passes %d, ended on the mid state %d\n", mid_passes, mid_taken);
+  if (c->spec_trace && ct.mid_passes)
+    fprintf(stderr, "mid-check passes %d, ended on the mid state %d\n", ct.mid_passes, ct.mid_taken);
   return TVL1_OK;
 }
 
@@ -1938,9 +1752,10 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
 
   BatchMask ubit{}, pbit{};
   std::vector<int64_t> level_iters((size_t)n * TVL1_MAX_LEVELS, 0), checks(n, 0), regathers(n, 0);
-  std::vector<int> nit(n), kb(n), hw;
-  std::vector<double> err(n), prev(n), prev_end(n);
-  std::vector<char> act(n), ends(n);
+  std::vector<WarpSched> sch(n);        // each pair's procOneScale state in the current warp
+  std::vector<WarpSched::Next> nx(n);   // ... and its next pass
+  std::vector<int> hw;
+  std::vector<char> act(n);
   // per pair: its previous warp on this level stopped at the first check, so this warp's
   // fused pass is predicted to stop there too and its constants are not stored (k_warp_iter's
   // store_c rule)
@@ -2026,9 +1841,7 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
       }
       int nact = 0;
       for (int b = 0; b < n; ++b) {
-        nit[b] = 0;
-        err[b] = DBL_MAX;
-        prev[b] = 0.0;
+        sch[b] = WarpSched{};
         act[b] = prm.iterations > 0;
         nact += act[b];
       }
@@ -2039,14 +1852,13 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
         regather.ubit = ubit;  // u^0: the set the fused pass read
         for (int b = 0; b < n; ++b) {
           const bool stored = stores(b);
-          nit[b] = 2;
+          sch[b].n = 2;
           ubit.flip(b);
           pbit.flip(b);
           pzero.clear(b);
-          err[b] = c->pinned[8 + b];
-          prev[b] = err[b];
+          sch[b].read(c->pinned[8 + b]);
           ++checks[b];
-          act[b] = err[b] > scaledEps && nit[b] < prm.iterations;
+          act[b] = sch[b].active(scaledEps, prm.iterations);
           nact += act[b];
           stopped_first[b] = !act[b];
           if (act[b] && !stored) regather.idx[regather.n++] = (uint8_t)b;
@@ -2059,18 +1871,14 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
         for (int b = 0; b < n; ++b) stopped_first[b] = 0;
       }
       while (nact > 0) {
-        // each active pair's pass (the single-pair rule, sched_after): k iterations up to and
+        // each active pair's pass (the single-pair rule, WarpSched): k iterations up to and
         // including its next check, at most kTbMax
         int kmin = kTbMax;
         for (int b = 0; b < n; ++b) {
-          kb[b] = 0;
-          ends[b] = 0;
+          nx[b] = WarpSched::Next{0, false, 0.0};
           if (!act[b]) continue;
-          bool ce = false;
-          kb[b] = sched_after(prev[b], scaledEps, nit[b], prm.iterations, kTbMax, prm.epsilon > 0, &ce,
-                              &prev_end[b]);
-          ends[b] = ce;
-          kmin = std::min(kmin, kb[b]);
+          nx[b] = sch[b].next(scaledEps, prm.iterations, kTbMax, prm.epsilon > 0);
+          kmin = std::min(kmin, nx[b].k);
         }
         // r4: pairs grouped by their pass length, one launch per group, so every pair runs
         // its whole pass.  TVL1_BATCH_GROUP=0 keeps r3's lock step: one launch of
@@ -2078,19 +1886,14 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
         // clipped to kmin iterations: no check).
         if (!c->batch_group)
           for (int b = 0; b < n; ++b)
-            if (act[b] && kb[b] > kmin) {
-              bool ce = false;
-              kb[b] = sched_after(prev[b], scaledEps, nit[b], prm.iterations, kmin, prm.epsilon > 0, &ce,
-                                  &prev_end[b]);
-              ends[b] = ce;
-            }
+            if (act[b] && nx[b].k > kmin) nx[b] = sch[b].next(scaledEps, prm.iterations, kmin, prm.epsilon > 0);
         for (int K = 1; K <= kTbMax; ++K) {
           BatchSel sel{};
           BatchSel chk{};
           for (int b = 0; b < n; ++b) {
-            if (!act[b] || kb[b] != K) continue;
+            if (!act[b] || nx[b].k != K) continue;
             sel.idx[sel.n++] = (uint8_t)b;
-            if (ends[b]) {
+            if (nx[b].calc_end) {
               sel.cerr.set(b);
               chk.idx[chk.n++] = (uint8_t)b;
             }
@@ -2108,32 +1911,29 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
         bool any_check = false;
         for (int b = 0; b < n; ++b) {
           if (!act[b]) continue;
-          prev[b] = prev_end[b];
-          nit[b] += kb[b];
+          sch[b].ran(nx[b]);
           ubit.flip(b);
           pbit.flip(b);
           pzero.clear(b);
-          err[b] = DBL_MAX;
-          any_check = any_check || ends[b];
+          any_check = any_check || nx[b].calc_end;
         }
         if (any_check) {
           HIP_TRY(c, hipEventRecord(c->ev_check[0], st));
           HIP_TRY(c, hipEventSynchronize(c->ev_check[0]));
           for (int b = 0; b < n; ++b) {
-            if (!act[b] || !ends[b]) continue;
-            err[b] = c->pinned[8 + b];
-            prev[b] = err[b];
+            if (!act[b] || !nx[b].calc_end) continue;
+            sch[b].read(c->pinned[8 + b]);
             ++checks[b];
           }
         }
         nact = 0;
         for (int b = 0; b < n; ++b) {
           if (!act[b]) continue;
-          act[b] = err[b] > scaledEps && nit[b] < prm.iterations;
+          act[b] = sch[b].active(scaledEps, prm.iterations);
           nact += act[b];
         }
       }
-      for (int b = 0; b < n; ++b) note_warp(b, s, wp, nit[b]);
+      for (int b = 0; b < n; ++b) note_warp(b, s, wp, sch[b].n);
     }
     HIP_TRY(c, hipGetLastError());
     if (s == 0) break;

@@ -2881,7 +2881,7 @@ struct CheckGate {
   int pk, pcalc;
 };
 
-// (procOneScale's schedule from a residual: sched_after, tvl1_plan.hpp)
+// (the gate's rule over procOneScale's schedule: gate_holds, tvl1_plan.hpp)
 TVL1_PLAIN __global__ void k_reduce(const double *__restrict__ partials, int n, double *__restrict__ out,
                          unsigned long long *seq_out, unsigned long long seq, CheckGate g) {
   if (gated_off(g.in, g.in_seq)) return;
@@ -2897,17 +2897,8 @@ TVL1_PLAIN __global__ void k_reduce(const double *__restrict__ partials, int n, 
   if (threadIdx.x == 0) {
     const double e = s[0];
     out[0] = e;
-    if (g.out) {
-      const bool ends = !(e > g.thr && g.n < g.iters);
-      bool ok = ends;
-      if (g.pk > 0) {
-        bool ce;
-        double pe;
-        const int k = sched_after(e, g.thr, g.n, g.iters, g.kmax, g.eps_pos, &ce, &pe);
-        ok = !ends && k == g.pk && (int)ce == g.pcalc;
-      }
-      *g.out = ok ? seq : 0ull;
-    }
+    if (g.out)
+      *g.out = gate_holds(e, g.thr, g.n, g.iters, g.kmax, g.eps_pos, g.pk, g.pcalc) ? seq : 0ull;
     if (seq_out) {
       __threadfence_system();
       *(volatile unsigned long long *)seq_out = seq;

@@ -4,9 +4,11 @@
 //
 // No HIP header: this compiles with any C++17 compiler, so tests/test_plan_cpu.py pins its
 // numbers on the CPU (tests/plan_dump.cpp).  Nothing here changes a result: segmentation and
-// speculation only decide how fast the same bits are computed, which is why the GPU parity
-// tests cannot see a slip in them.  tvl1_kernels.hpp includes this header for the constants the
-// kernels share with the plan and for sched_after, which k_reduce evaluates on the device.
+// the predictor's guesses only decide how fast the same bits are computed, which is why the GPU
+// parity tests cannot see a slip in them.  (The loop that acts on the guesses can change bits:
+// tvl1_walk.hpp, with a model test of its own.)  tvl1_kernels.hpp includes this header for the
+// constants the kernels share with the plan and for sched_after and gate_holds, which k_reduce
+// evaluates on the device.
 #pragma once
 
 #include <stdint.h>
@@ -57,6 +59,23 @@ TVL1_HD inline int sched_after(double prev, double thr, int n, int iters, int km
   *calc_end = ce;
   *prev_end = prev;
   return k;
+}
+
+// Whether the prediction (pk, pcalc) for what follows a check that read e at iteration count n
+// is what procOneScale does: pk = 0, the warp stops here; pk > 0, it continues
+// with a pass of pk iterations that ends in a check (pcalc) or not.  One definition for
+// k_reduce's evaluation of a speculation gate and for the host's verdict on its guess.
+TVL1_HD inline bool gate_holds(double e, double thr, int n, int iters, int kmax, int eps_pos, int pk,
+                               int pcalc) {
+  const bool ends = !(e > thr && n < iters);
+  bool ok = ends;
+  if (pk > 0) {
+    bool ce;
+    double pe;
+    const int k = sched_after(e, thr, n, iters, kmax, eps_pos, &ce, &pe);
+    ok = !ends && k == pk && (int)ce == pcalc;
+  }
+  return ok;
 }
 
 // Pyramid sizes exactly as calcImpl: round-half-even(cols*step), stop < 16.

@@ -1,5 +1,6 @@
-// plan_dump: prints what csrc/tvl1_plan.hpp plans for the cases of a file, one result line per
-// case line (tests/test_plan_cpu.py builds it with g++ and the host sanitizers; no GPU).
+// plan_dump: prints what csrc/tvl1_plan.hpp (and tvl1_walk.hpp's WarpSched) plans for the cases
+// of a file, one result line per case line (tests/test_plan_cpu.py builds it with g++ and the
+// host sanitizers; no GPU).
 //   seg bands rows k slots                                  -> seg_rows
 //   site NAME w h k px slots fill roll_seg pairs seg_min    -> bands seg_rows waves
 //   blocked w h k          -> iterate_blocks, then tiles_x out_h blocks of tb and of tb4
@@ -7,8 +8,8 @@
 //   pyr w h nscales step   -> L ws... hs...
 //   sched prev thr n iters kmax eps_pos        -> k calc_end prev_end   (doubles as %a)
 //   warp thr iters kmax eps_pos r1 r2 ...      -> the iteration counts of a warp's checks, '|',
-//        its iterations: the engine's host loop over sched_after; r_n (in units of thr) is the
-//        residual a check at iteration count n reads
+//        its iterations: WarpSched (csrc/tvl1_walk.hpp) stepped pass by pass; r_n (in units of
+//        thr) is the residual a check at iteration count n reads
 //   capsweep w0 w1 h0 h1   -> cases violations: every launch plan of every frame size in the
 //        range against the capacity reserved for that size
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include <string>
 
 #include "tvl1_plan.hpp"
+#include "tvl1_walk.hpp"
 
 using namespace tvl1k;
 
@@ -140,21 +142,16 @@ int main(int argc, char **argv) {
       const double thr = strtod(thr_s.c_str(), nullptr);
       std::vector<double> res(1, 0.0);   // res[n]: the residual read by a check at iteration count n
       while (ss >> r) res.push_back(strtod(r.c_str(), nullptr) * thr);
-      double error = DBL_MAX, prev = 0.0;
-      int n = 0;
-      while (error > thr && n < iters) {   // solve()'s warp loop without the launches
-        bool ce = false;
-        double pe = prev;
-        n += sched_after(prev, thr, n, iters, kmax, eps_pos, &ce, &pe);
-        if (ce) {
-          error = prev = res.at((size_t)n);
-          printf("%d ", n);
-        } else {
-          error = DBL_MAX;
-          prev = pe;
+      WarpSched w;   // the state every solve path keeps per warp
+      while (w.active(thr, iters)) {
+        const WarpSched::Next nx = w.next(thr, iters, kmax, eps_pos);
+        w.ran(nx);
+        if (nx.calc_end) {
+          w.read(res.at((size_t)w.n));
+          printf("%d ", w.n);
         }
       }
-      printf("| %d\n", n);
+      printf("| %d\n", w.n);
     } else if (cmd == "capsweep") {
       int w0, w1, h0, h1;
       ss >> w0 >> w1 >> h0 >> h1;

@@ -219,6 +219,39 @@ def test_speculation_same_schedule(built, monkeypatch, env, W, H, seed, kw):
 GOLDEN = __import__("pathlib").Path(__file__).resolve().parent / "golden"
 
 
+# The launch sequence of the single-pair solve, recorded from the engine before its warp loop
+# moved into walk_level (csrc/tvl1_walk.hpp): per-warp iterations, checks, wrong guesses, the
+# launches per class (profiling on, so the marks a wrong guess gives back count) and every
+# TVL1_SPEC_TRACE line -- each check's residual, the guess behind it and whether it held --
+# with speculation and mid-check passes together, as a solve alone on its device runs them.
+# The record is data (tests/golden/walk_sequence.json) and is never re-recorded from the code
+# under test: a line that differs is a change of behaviour.
+WALK_RECORD = __import__("json").loads((GOLDEN / "walk_sequence.json").read_text())
+
+
+@pytest.mark.parametrize("rec", WALK_RECORD, ids=lambda r: "%dx%d-%s-%s" % (
+    r["W"], r["H"], ",".join(f"{k}{v}" for k, v in r["params"].items()), r["env"] or "default"))
+def test_launch_sequence_as_recorded(built, monkeypatch, capfd, rec):
+    set_knobs(monkeypatch, rec["env"] + ",TVL1_SPEC_TRACE=1")
+    p = capi.make_params(**rec["params"])
+    I0, I1 = synth.gen_pair(rec["W"], rec["H"], seed=rec["seed"])
+    capfd.readouterr()
+    eng = capi.Engine(p)
+    eng.set_profiling(True)
+    u, v, st, wi = eng.calc_host(I0, I1)
+    eng.close()
+    err = capfd.readouterr().err
+    trace = [ln for ln in err.splitlines() if ln.startswith(("spec level", "mid-check"))]
+    assert [int(x) for x in wi.ravel()] == rec["warp_iterations"]
+    assert st["checks_total"] == rec["checks_total"]
+    assert st["speculation_misses"] == rec["speculation_misses"]
+    assert st["kernel_launches"] == rec["kernel_launches"]
+    assert trace == rec["trace"]
+    ur, vr, _, wr = checker.oracle_calc(I0, I1, p)
+    np.testing.assert_array_equal(wi, wr)
+    assert bits_equal(u, ur) and bits_equal(v, vr)
+
+
 @pytest.mark.parametrize("path", sorted(GOLDEN.glob("*.npz")), ids=lambda p: p.stem)
 def test_engine_reproduces_golden(engine, path):
     import json

@@ -64,9 +64,10 @@ def _ints(line):
 
 
 def test_plan_header_is_plain_cxx():
-    """No HIP header: the planner compiles with any C++17 compiler."""
-    text = (CSRC / "tvl1_plan.hpp").read_text()
-    assert "hip/" not in text and "__global__" not in text
+    """No HIP header: the planner and the level walker compile with any C++17 compiler."""
+    for name in ("tvl1_plan.hpp", "tvl1_walk.hpp"):
+        text = (CSRC / name).read_text()
+        assert "hip/" not in text and "__global__" not in text
 
 
 def _digest(lines):
