@@ -141,6 +141,14 @@ struct tvl1_ctx {
   int mid_slots = 0;         // resident k_iterate_roll_mid wavefronts
   int wi_nc = 2;             // TVL1_WI_NC: k_warp_iter consumer wavefronts (2: one per
                              // iteration of the pass; 1: both on one wave)
+  int stages = 1;            // TVL1_STAGES: k_iterate_stages (a wavefront per iteration).  1: the
+                             // 4-iteration passes k_iterate_tb4 would take; 2: every gamma = 0
+                             // pass of 2 or 4 iterations on every level (tests); 0: never
+  int stage_slots[kRollMax + 1] = {};   // resident k_iterate_stages<-, K> blocks per device
+  int stages_fill = 0;       // TVL1_STAGES_FILL: % of its resident blocks a k_iterate_stages launch
+                             // is sized for.  0: TVL1_FILL alone on the device, kStagesFillShared
+                             // while other solves share it (longer segments than the other
+                             // streaming launches take: a block's run-in is 3 K - 1 steps)
   // batch arena (tvl1_calc_batch): per logical plane, kBatchMax pairs' copies
   char *barena = nullptr;
   size_t barena_bytes = 0;
@@ -1048,6 +1056,38 @@ static int launch_roll(const Level &lv, const IterArgs &a, const PassReq &p, dou
   return sp.waves;
 }
 
+// the 2- or 4-iteration pass with a wavefront per iteration (k_iterate_stages, gamma = 0)
+static bool stages_take(const Level &lv, const PassReq &p) {
+  const tvl1_ctx *c = lv.c;
+  if (!c->stages || lv.gam || !lv.roll_ok || p.mid || (p.k != 2 && p.k != 4)) return false;
+  return c->stages == 2 || (p.k == 4 && !lv.roll_long && c->tb4);
+}
+static int launch_stages(const Level &lv, const IterArgs &a, const PassReq &p, double *hbm) {
+  tvl1_ctx *c = lv.c;
+  RollArgs ra;
+  ra.b = roll_bufs(c, lv.s, p.ui, p.pi, p.cb);
+  ra.it = a;
+  const StreamPlan sp =
+      plan_stages(lv.lw, lv.lh, p.k,
+                  fill_slots(c->stage_slots[p.k], c->stages_fill > 0       ? c->stages_fill
+                                                  : fill_now(c) == c->fill ? c->fill
+                                                                           : kStagesFillShared),
+                  c->roll_seg);
+  ra.bands = sp.bands;
+  ra.seg_rows = sp.seg_rows;
+  ra.waves = sp.waves;   // blocks: one residual partial each
+  if (partials_fit(c, sp.waves, sp.waves, "blocks") < 0) return -1;
+#define STAGES_M(FM)                                                                        \
+  if (p.k == 2)                                                                             \
+    hipLaunchKernelGGL((k_iterate_stages<FM, 2>), dim3(sp.waves), dim3(128), 0, lv.st, ra);  \
+  else                                                                                      \
+    hipLaunchKernelGGL((k_iterate_stages<FM, 4>), dim3(sp.waves), dim3(256), 0, lv.st, ra);
+  MATH_SWITCH(lv.math, STAGES_M)
+#undef STAGES_M
+  *hbm = stages_hbm(sp, lv.lh, p.k, (double)lv.lw * lv.lh, pass_planes(false, p.p_zero));
+  return sp.waves;
+}
+
 // blocked pass in 64 x 48 regions, 3 rows x 2 px per thread (k_iterate_tb4, gamma = 0)
 static int launch_tb4(const Level &lv, const IterArgs &a, const PassReq &p, double *hbm) {
   const BlockedPlan bp = tb4_plan(lv.lw, lv.lh, p.k);
@@ -1115,6 +1155,8 @@ static tvl1_status launch_pass(const Level &lv, const PassReq &p, int wp, int n,
     blocks = launch_warp_iter(lv, a, p, &hbm);
   else if (lv.exact_div)
     blocks = launch_iterate(lv, a, p, &hbm);
+  else if (stages_take(lv, p))
+    blocks = launch_stages(lv, a, p, &hbm);
   else if (lv.roll_ok && (p.k <= 2 || lv.roll_long))
     blocks = launch_roll(lv, a, p, &hbm);
   else if (c->tb4 && !lv.gam)
@@ -2235,6 +2277,8 @@ tvl1_status tvl1_create(tvl1_ctx **out, int device, const tvl1_params *params) {
   if (const char *m = getenv("TVL1_MID_MIN")) c->mid_min = atof(m);
   if (const char *m = getenv("TVL1_WI_NC")) c->wi_nc = atoi(m) == 1 ? 1 : 2;
   if (const char *m = getenv("TVL1_TB4")) c->tb4 = atoi(m) != 0;
+  if (const char *m = getenv("TVL1_STAGES")) c->stages = std::min(std::max(atoi(m), 0), 2);
+  if (const char *m = getenv("TVL1_STAGES_FILL")) c->stages_fill = std::max(0, atoi(m));
   if (const char *m = getenv("TVL1_POLL")) c->poll = atoi(m);
   if (const char *m = getenv("TVL1_SPEC")) c->spec = atoi(m);
   if (const char *m = getenv("TVL1_SPEC_TRACE")) c->spec_trace = atoi(m);
@@ -2287,6 +2331,8 @@ tvl1_status tvl1_create(tvl1_ctx **out, int device, const tvl1_params *params) {
     c->kb1_slots[2] = 4 * blocks_of((const void *)kb_iterate_roll<2, 1, kIEEE>, 256);
     c->kb1_slots[3] = 4 * blocks_of((const void *)kb_iterate_roll<3, 1, kIEEE>, 256);
     c->kb1_slots[4] = 4 * blocks_of((const void *)kb_iterate_roll<4, 1, kIEEE>, 256);
+    c->stage_slots[2] = blocks_of((const void *)k_iterate_stages<kIEEE, 2>, 128);
+    c->stage_slots[4] = blocks_of((const void *)k_iterate_stages<kIEEE, 4>, 256);
     c->warp_ring_slots = blocks_of((const void *)k_warp_ring<6, 2>, 128);
     c->witer_slots = c->wi_nc == 2 ? blocks_of((const void *)k_warp_iter<kWiMargin, 0, 128, 1, 2>, 256)
                                    : blocks_of((const void *)k_warp_iter<kWiMargin, 0, 128, 1, 1>, 192);

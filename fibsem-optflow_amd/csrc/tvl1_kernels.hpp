@@ -2860,6 +2860,251 @@ __global__ __launch_bounds__(64 * NC + BW) void k_warp_iter(WarpIterArgs w) {
   warp_iter_body<M, FM, BW, PRIO, NC>(w, wid, ring, cring, hring);
 }
 
+// ---------------------------------------------------------------- K6+K8, a wavefront per iteration
+// k_iterate_stages<FM, K>: the K = 2 or 4 iterations of a gamma = 0 pass on K wavefronts of one
+// block, which owns a k_iterate_roll<false, K, 2> band (128 px: 2 px per lane, roll_halo<K, 2>
+// px of halo a side) over a segment of rows.  Wavefront n - 1 runs iteration n over the whole
+// band, one row per step, so x neighbours stay DPP shifts and y neighbours the stage's own
+// last row in registers (k_warp_iter's two-consumer form, for any stage).  At step t (input
+// row r0 + t) stage n works on row y = r0 + t - 2 (n - 1): u^n(y) and p^n(y - 1), exactly
+// roll_advance's operations on its operands (stage_row is its stage n), so the same bits.
+//   * Stage 1 loads u^0, p^0 and the warp constants of its row from HBM (a 3-row register
+//     ring, p = +0 from kOOB on a level's first pass) and puts the constants in the C ring
+//     (LDS, stages_crows<K>() rows > the 2 (K - 1) rows the last stage lags behind).
+//   * Stage n hands u^n(y) and p^n(y - 1) (6 planes, 2 slots) to stage n + 1, which reads the
+//     slot one barrier later and keeps u^n(y) for its next step (its row is y - 1).
+//   * Stage K stores u^K and p^K of the segment's rows and sums the residual.
+// One LDS-only barrier per step orders each hand-off slot's write before its read (and the
+// read before the slot's next write two steps later).  A stage is idle (barrier only) before
+// row r0 - 1 and after row ye + K - n, the last one a stored cell depends on.  The LDS starts
+// zeroed, so the step at row r0 - 1 (it only has to keep the hand-off's u and p) reads zeros
+// where roll_advance's first steps read zeroed registers.  LDS: 30 KiB (K = 4), 12 KiB (K = 2).
+constexpr int kStagesH = 6;                    // hand-off planes: u1, u2, p11, p12, p21, p22
+constexpr int kStagesBW = 128;                 // band width (px)
+constexpr int kStagesSlot = kStagesH * kStagesBW;   // floats of a hand-off slot
+constexpr int kStagesCRow = 3 * kStagesBW;          // floats of a C ring row
+template <int K>
+constexpr int stages_crows() { return K <= 2 ? 4 : 8; }   // a power of two > 2 (K - 1)
+template <int K>
+constexpr int stages_lds_floats() { return stages_crows<K>() * kStagesCRow + (K - 1) * 2 * kStagesSlot; }
+
+struct StageRegs {   // stage n between its steps at rows y and y + 1
+  float Uo1[2], Uo2[2];                      // u^{n-1}(y + 1) (stages > 1: kept from the hand-off)
+  float P11p[2], P12p[2], P21p[2], P22p[2];  // p^{n-1}(y)
+  float U1p[2], U2p[2];                      // u^n(y)
+};
+
+// Stage n at row y: u^n(y) from u^{n-1}(y) (uo), p^{n-1}(y) (p..) and p^{n-1}(y - 1); p^n(y - 1)
+// from u^n(y - 1), u^n(y) and p^{n-1}(y - 1).  LAST: stores both and sums the residual;
+// otherwise they go to the hand-off slot hout.
+template <int FM, bool LAST>
+__device__ __forceinline__ void stage_row(StageRegs &S, const float (&wx)[2], const float (&wy)[2],
+                                          const float (&rh)[2], const float (&uo1)[2],
+                                          const float (&uo2)[2], const float (&p11)[2],
+                                          const float (&p12)[2], const float (&p21)[2],
+                                          const float (&p22)[2], float *__restrict__ hout,
+                                          const IterArgs &a, const RollBufs &B, int y,
+                                          const RollLane &L, unsigned rowb, double &acc) {
+  constexpr int PX = 2, BW = kStagesBW;
+  const unsigned ps = B.pstride;
+  const bool stU = L.out && y >= L.ys && y < L.ye;
+  float n1[PX], n2[PX];
+#pragma unroll
+  for (int j = 0; j < PX; ++j) {
+    float n3;
+    estimate_u_px<false, FM, false, true>(wx[j], wy[j], rh[j], uo1[j], uo2[j], 0.0f, p11[j],
+                                          left_of<PX>(p11, j), p12[j], S.P12p[j], p21[j],
+                                          left_of<PX>(p21, j), p22[j], S.P22p[j], 0.0f, 0.0f, 0.0f,
+                                          0.0f, L.X + j, y, a, n1[j], n2[j], n3, L.c0);
+    if (LAST && a.calc_err) {
+      const float e = residual_px<FM>(uo1[j] - n1[j], uo2[j] - n2[j]);
+      acc += stU && L.X + j < a.W ? (double)e : 0.0;
+    }
+  }
+  if (LAST) {
+    const unsigned vo = stU ? (unsigned)y * rowb + L.vst : kOOB;
+    bstorev<PX>(B.ud, B.ub, vo, n1);
+    bstorev<PX>(B.ud, B.ub, vo, n2, ps);
+  }
+  if (y >= a.H) {   // u below the image repeats row H-1 (roll_advance)
+#pragma unroll
+    for (int j = 0; j < PX; ++j) { n1[j] = S.U1p[j]; n2[j] = S.U2p[j]; }
+  }
+  const int yD = y - 1;
+  float o11[PX], o12[PX], o21[PX], o22[PX];
+#pragma unroll
+  for (int j = 0; j < PX; ++j) {
+    const bool has_right = L.X + j + 1 < a.W;
+    dual_px<false, false, FM>(S.U1p[j], right_of<PX>(S.U1p, j), n1[j], has_right, true, a.taut,
+                              S.P11p[j], S.P12p[j], o11[j], o12[j], a.taut_small);
+    dual_px<false, false, FM>(S.U2p[j], right_of<PX>(S.U2p, j), n2[j], has_right, true, a.taut,
+                              S.P21p[j], S.P22p[j], o21[j], o22[j], a.taut_small);
+  }
+  if (LAST) {
+    const unsigned vo = L.out && yD >= L.ys && yD < L.ye ? (unsigned)yD * rowb + L.vst : kOOB;
+    bstorev<PX>(B.pd, B.pb, vo, o11);
+    bstorev<PX>(B.pd, B.pb, vo, o12, ps);
+    bstorev<PX>(B.pd, B.pb, vo, o21, 2 * ps);
+    bstorev<PX>(B.pd, B.pb, vo, o22, 3 * ps);
+  } else {
+    if (yD < 0) {   // p above the image is +0 (roll_advance)
+#pragma unroll
+      for (int j = 0; j < PX; ++j) o11[j] = o12[j] = o21[j] = o22[j] = 0.0f;
+    }
+    lds_put<PX>(hout, n1);
+    lds_put<PX>(hout + BW, n2);
+    lds_put<PX>(hout + 2 * BW, o11);
+    lds_put<PX>(hout + 3 * BW, o12);
+    lds_put<PX>(hout + 4 * BW, o21);
+    lds_put<PX>(hout + 5 * BW, o22);
+  }
+#pragma unroll
+  for (int j = 0; j < PX; ++j) {
+    S.U1p[j] = n1[j]; S.U2p[j] = n2[j];
+    S.P11p[j] = p11[j]; S.P12p[j] = p12[j]; S.P21p[j] = p21[j]; S.P22p[j] = p22[j];
+  }
+}
+
+// Stage 1's step t at input row r (in `cur`); row r + kRollAhead is loaded into `ahead`.
+template <int FM, int K>
+__device__ __forceinline__ void stage_first_step(StageRegs &S, float *__restrict__ cring,
+                                                 float *__restrict__ hring,
+                                                 const RollIn<false, 2> &cur, RollIn<false, 2> &ahead,
+                                                 const IterArgs &a, const RollBufs &B, int r, int t,
+                                                 bool active, const RollLane &L, int lane,
+                                                 unsigned rowb) {
+  roll_load<false, 2>(ahead, B, (unsigned)imin(r + kRollAhead, a.H - 1) * rowb, L.vload, L.vloadp);
+  __builtin_amdgcn_sched_barrier(0);
+  lds_barrier();   // the slots written below were read at the previous step
+  if (active) {
+    float *c = cring + (r & (stages_crows<K>() - 1)) * kStagesCRow + 2 * lane;
+    lds_put<2>(c, cur.wx);
+    lds_put<2>(c + kStagesBW, cur.wy);
+    lds_put<2>(c + 2 * kStagesBW, cur.rh);
+    double none = 0.0;
+    stage_row<FM, false>(S, cur.wx, cur.wy, cur.rh, cur.u1, cur.u2, cur.p11, cur.p12, cur.p21,
+                         cur.p22, hring + (t & 1) * kStagesSlot + 2 * lane, a, B, r, L, rowb, none);
+  }
+}
+
+// Step t of stage n > 1 at row y: hin is the ring stage n - 1 writes, hout the one stage n + 1
+// reads (LAST: none).
+template <int FM, int K, bool LAST>
+__device__ __forceinline__ void stage_next_step(StageRegs &S, const float *__restrict__ cring,
+                                                const float *__restrict__ hin,
+                                                float *__restrict__ hout, const IterArgs &a,
+                                                const RollBufs &B, int y, int t, bool active,
+                                                const RollLane &L, int lane, unsigned rowb,
+                                                double &acc) {
+  lds_barrier();   // the hand-off written at the previous step
+  if (active) {
+    constexpr int BW = kStagesBW;
+    const float *h = hin + ((t + 1) & 1) * kStagesSlot + 2 * lane;
+    float u1[2], u2[2], p11[2], p12[2], p21[2], p22[2], wx[2], wy[2], rh[2];
+    lds_get<2>(u1, h);
+    lds_get<2>(u2, h + BW);
+    lds_get<2>(p11, h + 2 * BW);
+    lds_get<2>(p12, h + 3 * BW);
+    lds_get<2>(p21, h + 4 * BW);
+    lds_get<2>(p22, h + 5 * BW);
+    const float *c = cring + (y & (stages_crows<K>() - 1)) * kStagesCRow + 2 * lane;
+    lds_get<2>(wx, c);
+    lds_get<2>(wy, c + BW);
+    lds_get<2>(rh, c + 2 * BW);
+    stage_row<FM, LAST>(S, wx, wy, rh, S.Uo1, S.Uo2, p11, p12, p21, p22,
+                        LAST ? nullptr : hout + (t & 1) * kStagesSlot + 2 * lane, a, B, y, L, rowb, acc);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { S.Uo1[j] = u1[j]; S.Uo2[j] = u2[j]; }
+  }
+}
+
+// steps of a segment's block: the last stage reaches row ye (p^K(ye - 1)), 2 (K - 1) steps
+// behind stage 1, in whole trips of the 3-row load ring (stages_steps, tvl1_plan.hpp)
+template <int FM, int K>
+__global__ __launch_bounds__(64 * K) void k_iterate_stages(RollArgs ra) {
+  static_assert(K == 2 || K == 4, "one wavefront per iteration of a 2- or 4-iteration pass");
+  static_assert(kRollAhead == 2, "the step loops are unrolled for a 3-row ring");
+  static_assert(stages_lds_floats<K>() * 4 <= 32768, "5 blocks per CU");
+  constexpr int PX = 2, BW = kStagesBW, HALO = roll_halo<K, PX>();
+  constexpr int NF = stages_lds_floats<K>();
+  __shared__ __attribute__((aligned(16))) float lds[NF];
+  const int wid = __builtin_amdgcn_readfirstlane(xcd_chunk(blockIdx.x, gridDim.x));
+  if (wid >= ra.waves || gated_off(ra.it.gate, ra.it.gate_seq)) return;   // whole blocks
+  for (int i = threadIdx.x; i < NF / 4; i += 64 * K)
+    reinterpret_cast<float4 *>(lds)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float *cring = lds, *hring = lds + stages_crows<K>() * kStagesCRow;
+  const IterArgs &a = ra.it;
+  const RollBufs &B = ra.b;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int band = wid % ra.bands, seg = wid / ra.bands;
+  const int X0 = band * (BW - 2 * HALO) - HALO;
+  RollLane L;
+  L.X = X0 + PX * lane;
+  L.vload = 4u * imin(imax(L.X, 0), a.P - PX);
+  L.vloadp = a.p_zero ? kOOB : L.vload;
+  L.out = PX * lane >= HALO && PX * lane < BW - HALO && L.X < a.W;
+  L.vst = 4u * (unsigned)imax(L.X, 0);
+  L.ys = seg * ra.seg_rows;
+  L.ye = imin(L.ys + ra.seg_rows, a.H);
+  L.c0 = X0 <= 0;
+  const unsigned rowb = 4u * (unsigned)a.P;
+  const int r0 = stages_r0(L.ys, K);
+  const int thirds = stages_steps(L.ys, L.ye, K) / 3;
+  StageRegs S;
+#pragma unroll
+  for (int j = 0; j < PX; ++j) {
+    S.Uo1[j] = S.Uo2[j] = S.U1p[j] = S.U2p[j] = 0.0f;
+    S.P11p[j] = S.P12p[j] = S.P21p[j] = S.P22p[j] = 0.0f;
+  }
+  lds_barrier();   // the zero fill
+  if (wv == 0) {
+    const int yend = L.ye + K - 1;
+    RollIn<false, 2> A, Bx, C;
+    roll_load<false, 2>(A, B, (unsigned)r0 * rowb, L.vload, L.vloadp);
+    roll_load<false, 2>(Bx, B, (unsigned)imin(r0 + 1, a.H - 1) * rowb, L.vload, L.vloadp);
+    for (int h = 0, t = 0; h < thirds; ++h, t += 3) {
+      progress_prio<1>(h, thirds);
+      const int r = r0 + t;
+      stage_first_step<FM, K>(S, cring, hring, A, C, a, B, r, t, r <= yend, L, lane, rowb);
+      stage_first_step<FM, K>(S, cring, hring, Bx, A, a, B, r + 1, t + 1, r + 1 <= yend, L, lane, rowb);
+      stage_first_step<FM, K>(S, cring, hring, C, Bx, a, B, r + 2, t + 2, r + 2 <= yend, L, lane, rowb);
+    }
+  } else if (wv == K - 1) {
+    const float *hin = hring + (K - 2) * 2 * kStagesSlot;
+    double acc = 0.0;
+    for (int h = 0, t = 0; h < thirds; ++h, t += 3) {
+      progress_prio<1>(h, thirds);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int y = r0 + t + i - 2 * (K - 1);
+        stage_next_step<FM, K, true>(S, cring, hin, nullptr, a, B, y, t + i, y >= r0 - 1 && y <= L.ye,
+                                     L, lane, rowb, acc);
+      }
+    }
+    if (a.calc_err) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+      if (lane == 0) a.partials[wid] = acc;
+    }
+  } else if (K > 2) {
+    const int n = wv + 1;
+    const float *hin = hring + (n - 2) * 2 * kStagesSlot;
+    float *hout = hring + (n - 1) * 2 * kStagesSlot;
+    const int yend = L.ye + K - n;
+    double none = 0.0;
+    for (int h = 0, t = 0; h < thirds; ++h, t += 3) {
+      progress_prio<1>(h, thirds);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int y = r0 + t + i - 2 * (n - 1);
+        stage_next_step<FM, K, false>(S, cring, hin, hout, a, B, y, t + i, y >= r0 - 1 && y <= yend,
+                                      L, lane, rowb, none);
+      }
+    }
+  }
+}
+
 // K7: fixed-order sum of the per-block partials (one block).
 // The residual goes to coherent host memory; with seq_out set, the check's sequence number
 // follows it there (after a system-scope fence), so the host can poll for it instead of

@@ -168,6 +168,26 @@ inline StreamPlan plan_roll(int lw, int lh, int k, int px, int slots, int roll_s
   return stream_plan(lw, lh, 64 * px - 2 * roll_halo_of(k, px), k, slots, roll_seg, seg_floor, pairs);
 }
 
+// k_iterate_stages<FM, K> (K = 2 or 4, gamma = 0): a block of K wavefronts per 128-px band
+// (2 px per lane, the halo of k_iterate_roll<false, K, 2>) and segment; stage n works 2 (n - 1)
+// rows behind stage 1.  A segment's block starts at input row stages_r0 and runs
+// stages_steps steps (whole trips of stage 1's 3-row load ring): stage 1 has then passed row
+// ye - 1 + K and the last stage row ye, where it stores p^K(ye - 1).
+TVL1_HD inline int stages_r0(int ys, int k) { return ys - k > 0 ? ys - k : 0; }
+TVL1_HD inline int stages_steps(int ys, int ye, int k) {
+  return (ye - stages_r0(ys, k) + 2 * k - 1 + 2) / 3 * 3;
+}
+// share of the resident blocks a launch is sized for while other solves share the device
+// (TVL1_FILL_SHARED's 60 % gives 47-row segments on a 4.2 Mpx level, 1.23 x their rows in
+// steps; 45 %: 63 rows, 1.17 x)
+constexpr int kStagesFillShared = 45;
+constexpr int stages_out_w(int k) { return 128 - 2 * roll_halo_of(k, 2); }
+// slots: the resident blocks the launch is sized for.  roll_segment's cost of a segment is
+// rows + 2 k' steps; a stage block runs rows + 3 K - 1, so k' = ceil(3 K / 2)
+inline StreamPlan plan_stages(int lw, int lh, int k, int slots, int roll_seg) {
+  return stream_plan(lw, lh, stages_out_w(k), (3 * k + 1) / 2, slots, roll_seg);
+}
+
 // ---------------------------------------------------------------- blocked passes
 // k_iterate (one iteration, exact division): blocks of 4 wave strips
 inline int iterate_blocks(int W, int H) {
@@ -266,6 +286,11 @@ inline double batch_warp_iter_hbm(const StreamPlan &p, int lh, int ww, double Nl
 inline double roll_hbm(const StreamPlan &p, int lh, int k, int px, double Nl, const PassPlanes &pl) {
   const double rows = rows_with_halo(lh, p.seg_rows, k);
   return (double)p.bands * 64.0 * px * rows * 4.0 * pl.ld + Nl * 4.0 * pl.st;
+}
+// k_iterate_stages<FM, k>: stage 1 loads what k_iterate_roll<false, k, 2>'s wavefront loads (the
+// later stages read LDS only), the last stage stores the interior
+inline double stages_hbm(const StreamPlan &p, int lh, int k, double Nl, const PassPlanes &pl) {
+  return roll_hbm(p, lh, k, 2, Nl, pl);
 }
 // ... of kb_iterate_roll's n pairs (gamma = 0), nz of them with p = 0
 inline double batch_roll_hbm(const StreamPlan &p, int lh, int k, int px, double Nl, int n, int nz) {
