@@ -23,17 +23,18 @@
 // reference's: the same inputs (JSON keys with their defaults), an affine that maps frame1
 // onto frame0, the same rejection rules and messages.  This pipeline itself is restated
 // bit for bit by oracle/tvl1_oracle_align.c (test infrastructure): keypoints, descriptors,
-// the 2-NN match list, the fit and the warps are compared exactly (tests/test_align_gpu.py),
-// and known affine motions of synthetic slices are recovered.
+// the 2-NN match list, the fit and the warps are compared exactly (tests/test_align_gpu.py;
+// at every tile, level, segment and budget edge: tests/test_gpu_align_edges.py), and known
+// affine motions of synthetic slices are recovered.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-namespace tvl1k {
+#include "tvl1_align_plan.hpp"   // kOrbHalf, kOrbBits, SelLevel, OrbKp, Top2, the host plan
 
-constexpr int kOrbPatch = 31, kOrbHalf = 15, kOrbBits = 256;
+namespace tvl1k {
 
 // FAST-9 on a float level image (values 0..255) at px (x, y): a contiguous arc of >= 9 of
 // the 16 radius-3 circle px all brighter than c + t or all darker than c - t.
@@ -175,10 +176,7 @@ __global__ void __launch_bounds__(256) ka_nms(const float *__restrict__ score, i
 // KeyPointsFilter::retainBest per level: the quota largest keys of each level, by an MSB-first
 // radix select (8 passes of 8 bits, histograms in LDS) to the quota-th largest key T, then
 // every key >= T copied out (exactly quota of them: keys are unique).  One workgroup per
-// level; the host orders the <= quota survivors.
-struct SelLevel {
-  unsigned off, cap, quota;
-};
+// level; the host orders the <= quota survivors.  (SelLevel: tvl1_align_plan.hpp.)
 __global__ void __launch_bounds__(1024) ka_select(const uint64_t *__restrict__ keys,
                                                   const unsigned *__restrict__ count,
                                                   const SelLevel *__restrict__ lv,
@@ -235,12 +233,6 @@ __global__ void __launch_bounds__(1024) ka_select(const uint64_t *__restrict__ k
   if (t == 0) nsel[l] = s_n;
 }
 
-struct OrbKp {
-  float x, y;        // level coordinates
-  float angle;       // radians (filled by ka_describe)
-  int level;
-};
-
 // Orientation (intensity centroid over the radius-15 disc) and the 256-bit rotated BRIEF
 // descriptor of each keypoint; one thread per keypoint.  pat: 256 x (ax, ay, bx, by).
 __global__ void ka_describe(const float *const *__restrict__ levels, const int *__restrict__ lP,
@@ -287,10 +279,7 @@ __global__ void ka_describe(const float *const *__restrict__ levels, const int *
 // holds 64 queries in registers and streams its train segment through LDS, 64 descriptors
 // per tile; each segment's stable top-2 (ties: lower train index) goes to part[], and
 // ka_match2_merge folds the segments in index order, which gives exactly the top-2 of one
-// sequential scan.
-struct Top2 {
-  int b0, b1, d0, d1;
-};
+// sequential scan.  (Top2: tvl1_align_plan.hpp.)
 __device__ __forceinline__ void top2_push(Top2 &t, int h, int j) {
   if (h < t.d0) {
     t.d1 = t.d0;

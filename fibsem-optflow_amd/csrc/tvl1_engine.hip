@@ -25,6 +25,7 @@
 #include "tvl1_walk.hpp"
 #include "tvl1_kernels.hpp"
 #include "tvl1_batch.hpp"
+#include "tvl1_align_plan.hpp"
 #include "tvl1_align.hpp"
 #include "tvl1_stack.hpp"
 #include "tvl1_shift.hpp"
@@ -2012,52 +2013,13 @@ struct OrbSet {
   uint32_t *desc = nullptr;   // device, 8 words per keypoint (in the ctx's align scratch)
 };
 
-// One frame's ORB pyramid geometry and its quota per level (ORB_Impl::detectAndCompute:
-// nfeatures * (1 - f) / (1 - f^L) * f^l, the remainder on the last level).
-struct OrbGeom {
-  int L = 0;
-  std::vector<int> w, h, p, quota;
-  std::vector<unsigned> cap, off;   // key-list capacity / offset per level
-  size_t keys = 0, lev_floats = 0;
-  unsigned kmax = 0;
-};
-
+// The pyramid geometry, the quotas and the scratch layout are planned in
+// tvl1_align_plan.hpp (HIP-free); here the layout's offsets become pointers.
 static OrbGeom orb_geom(int W, int H, const tvl1_align_params &ap) {
-  OrbGeom g;
-  g.L = std::max(1, ap.nlevels);
-  const double sf = ap.scale_factor;
-  g.w.resize(g.L);
-  g.h.resize(g.L);
-  g.p.resize(g.L);
-  g.quota.assign(g.L, 0);
-  g.cap.resize(g.L);
-  g.off.resize(g.L);
-  for (int l = 0; l < g.L; ++l) {
-    const double scale = 1.0 / std::pow(sf, l - ap.first_level);
-    g.w[l] = l == 0 ? W : std::max(1, (int)std::lrint(W * scale));
-    g.h[l] = l == 0 ? H : std::max(1, (int)std::lrint(H * scale));
-    g.p[l] = (int)align_up((size_t)g.w[l], 64);
-    g.lev_floats += align_up((size_t)g.p[l] * g.h[l], 64);
-    g.cap[l] = (unsigned)(((size_t)g.w[l] + 1) / 2 * (((size_t)g.h[l] + 1) / 2));
-    g.off[l] = (unsigned)g.keys;
-    g.keys += align_up(g.cap[l], 32);
-  }
-  const double f = 1.0 / sf;
-  double nd = ap.nfeatures * (1 - f) / (1 - std::pow(f, g.L));
-  int sum = 0;
-  for (int l = 0; l < g.L - 1; ++l) {
-    g.quota[l] = (int)std::lrint(nd);
-    sum += g.quota[l];
-    nd *= f;
-  }
-  g.quota[g.L - 1] = std::max(ap.nfeatures - sum, 0);
-  for (int l = 0; l < g.L; ++l) g.kmax = std::max(g.kmax, (unsigned)g.quota[l]);
-  return g;
+  return tvl1k::orb_geom(W, H, ap.nfeatures, ap.scale_factor, ap.nlevels, ap.first_level);
 }
 
-// The align scratch: [kps | desc q | desc t | match best | match dist | pyramid | blurred
-// pyramid | score | keys | counts | selected keys | nsel | level table], carved per frame.
-struct AlignCarve {
+struct AlignPtrs {
   float *lev = nullptr, *blur = nullptr, *score = nullptr;
   uint64_t *keys = nullptr, *sel = nullptr;
   unsigned *cnt = nullptr, *nsel = nullptr;
@@ -2069,40 +2031,34 @@ struct AlignCarve {
   int2 *best = nullptr, *dist = nullptr;
   Top2 *part = nullptr;
 };
-constexpr int kMatchSegs = 16;   // train segments of ka_match2 (grid y)
+static_assert(sizeof(int2) == 2 * sizeof(int32_t), "int2 layout");
 
-static size_t align_carve(char *base, const OrbGeom &g, bool blur, int nfeat, AlignCarve &cv) {
-  size_t o = 0;
-  auto take = [&](size_t bytes) -> char * {
-    char *p = base ? base + o : nullptr;
-    o += align_up(std::max<size_t>(bytes, 1), 256);
-    return p;
-  };
-  // geometry-independent parts first: the two frames' carves share them
-  cv.kps = (OrbKp *)take((size_t)nfeat * sizeof(OrbKp));
-  cv.desc[0] = (uint32_t *)take((size_t)nfeat * 32);
-  cv.desc[1] = (uint32_t *)take((size_t)nfeat * 32);
-  cv.best = (int2 *)take((size_t)nfeat * sizeof(int2));
-  cv.dist = (int2 *)take((size_t)nfeat * sizeof(int2));
-  cv.part = (Top2 *)take((size_t)nfeat * kMatchSegs * sizeof(Top2));
-  cv.lev = (float *)take(g.lev_floats * 4);
-  cv.blur = blur ? (float *)take(g.lev_floats * 4) : nullptr;
-  cv.score = (float *)take((size_t)g.w[0] * g.h[0] * 4);
-  cv.keys = (uint64_t *)take(g.keys * 8);
-  cv.cnt = (unsigned *)take(g.L * 4);
-  cv.sel = (uint64_t *)take((size_t)g.L * g.kmax * 8);
-  cv.nsel = (unsigned *)take(g.L * 4);
-  cv.lv = (SelLevel *)take(g.L * sizeof(SelLevel));
-  cv.dlev = (float **)take(g.L * sizeof(float *));
-  cv.dlp = (int *)take(g.L * 4);
-  return o;
+static AlignPtrs align_ptrs(char *base, const AlignCarve &a) {
+  AlignPtrs cv;
+  cv.kps = (OrbKp *)(base + a.kps);
+  cv.desc[0] = (uint32_t *)(base + a.desc[0]);
+  cv.desc[1] = (uint32_t *)(base + a.desc[1]);
+  cv.best = (int2 *)(base + a.best);
+  cv.dist = (int2 *)(base + a.dist);
+  cv.part = (Top2 *)(base + a.part);
+  cv.lev = (float *)(base + a.lev);
+  cv.blur = a.blur != AlignCarve::kNone ? (float *)(base + a.blur) : nullptr;
+  cv.score = (float *)(base + a.score);
+  cv.keys = (uint64_t *)(base + a.keys);
+  cv.cnt = (unsigned *)(base + a.cnt);
+  cv.sel = (uint64_t *)(base + a.sel);
+  cv.nsel = (unsigned *)(base + a.nsel);
+  cv.lv = (SelLevel *)(base + a.lv);
+  cv.dlev = (float **)(base + a.dlev);
+  cv.dlp = (int *)(base + a.dlp);
+  return cv;
 }
 
 // ORB detect + describe of one frame (cv::cuda::ORB::detectAndCompute, features.cpp:60-61)
 // into out; descriptors go to desc.  All levels are queued back to back: one host sync for
 // the selected keys, one for the descriptors.
 static tvl1_status orb_detect(tvl1_ctx *c, const uint8_t *img, size_t pitch, const OrbGeom &g,
-                              const tvl1_align_params &ap, const AlignCarve &cv, uint32_t *desc,
+                              const tvl1_align_params &ap, const AlignPtrs &cv, uint32_t *desc,
                               OrbSet &out, hipStream_t st, bool angles = false) {
   const int L = g.L, W = g.w[0], H = g.h[0];
   std::vector<float *> lev(L);
@@ -2120,12 +2076,12 @@ static tvl1_status orb_detect(tvl1_ctx *c, const uint8_t *img, size_t pitch, con
                        nullptr, g.w[l - 1], g.h[l - 1], g.p[l - 1], lev[l], nullptr, nullptr,
                        g.w[l], g.h[l], g.p[l], (double)g.w[l - 1] / g.w[l],
                        (double)g.h[l - 1] / g.h[l], 0, 0, 1.0f);
-  const int border = std::max(ap.edge_threshold, kOrbHalf + 1);
+  const int border = orb_border(ap.edge_threshold);
   std::vector<SelLevel> lv(L);
   HIP_TRY(c, hipMemsetAsync(cv.cnt, 0, L * sizeof(unsigned), st));
   for (int l = 0; l < L; ++l) {
     lv[l] = SelLevel{g.off[l], g.cap[l], (unsigned)g.quota[l]};
-    if (g.w[l] <= 2 * border || g.h[l] <= 2 * border || g.quota[l] == 0) {
+    if (orb_level_skipped(g, l, border)) {
       lv[l].quota = 0;
       lv[l].cap = 0;
       continue;
@@ -2588,9 +2544,10 @@ tvl1_status tvl1_find_alignment(tvl1_ctx *c, const uint8_t *frame1, size_t pitch
   }
   const OrbGeom g1 = orb_geom(w1, h1, *ap), g0 = orb_geom(w0, h0, *ap);
   const bool blur = ap->blur_for_descriptor != 0;
-  AlignCarve cv;
-  const size_t need = std::max(align_carve(nullptr, g1, blur, ap->nfeatures, cv),
-                               align_carve(nullptr, g0, blur, ap->nfeatures, cv));
+  // one per-keypoint capacity for both frames (the quota sum can exceed nfeatures)
+  const int kcap = std::max(g1.kcap, g0.kcap);
+  const AlignCarve a1 = align_carve(g1, blur, kcap), a0 = align_carve(g0, blur, kcap);
+  const size_t need = std::max(a1.bytes, a0.bytes);
   if (need > c->align_bytes) {
     const tvl1_status r = arena_alloc(c, &c->align_scratch, &c->align_bytes, need, st);
     if (r != TVL1_OK) return r;
@@ -2602,23 +2559,21 @@ tvl1_status tvl1_find_alignment(tvl1_ctx *c, const uint8_t *frame1, size_t pitch
   // query = frame1, train = frame0 (find_alignment(frame1_GPU, frame0_GPU)); the two frames
   // share the scratch's pyramid and keys and keep their descriptors apart
   OrbSet q, t;
-  align_carve(c->align_scratch, g1, blur, ap->nfeatures, cv);
+  const AlignPtrs cv = align_ptrs(c->align_scratch, a1);
   tvl1_status s = orb_detect(c, frame1, pitch1, g1, *ap, cv, cv.desc[0], q, st);
   const auto t1 = now();
-  AlignCarve cv0;
-  align_carve(c->align_scratch, g0, blur, ap->nfeatures, cv0);
+  const AlignPtrs cv0 = align_ptrs(c->align_scratch, a0);
   if (s == TVL1_OK) s = orb_detect(c, frame0, pitch0, g0, *ap, cv0, cv0.desc[1], t, st);
   const auto t2 = now();
   if (s != TVL1_OK) return s;
   std::vector<int2> best, dist;
   const int nq = (int)q.kps.size(), nt = (int)t.kps.size();
   if (nq > 0 && nt > 0) {
-    const int nseg = std::max(1, std::min(kMatchSegs, (nt + 255) / 256));
-    const int seg = (int)align_up((size_t)((nt + nseg - 1) / nseg), 64);
-    hipLaunchKernelGGL(ka_match2, dim3((nq + 63) / 64, nseg), dim3(64), 0, st, q.desc, nq,
-                       t.desc, nt, seg, cv.part);
+    const MatchPlan mp = match_plan(nt);
+    hipLaunchKernelGGL(ka_match2, dim3((nq + 63) / 64, mp.nseg), dim3(64), 0, st, q.desc, nq,
+                       t.desc, nt, mp.seg, cv.part);
     hipLaunchKernelGGL(ka_match2_merge, dim3((nq + 255) / 256), dim3(256), 0, st, cv.part, nq,
-                       nseg, cv.best, cv.dist);
+                       mp.nseg, cv.best, cv.dist);
     best.resize(nq);
     dist.resize(nq);
     HIP_TRY(c, hipMemcpyAsync(best.data(), cv.best, nq * sizeof(int2), hipMemcpyDeviceToHost, st));
@@ -2683,13 +2638,13 @@ tvl1_status tvl1_orb_detect(tvl1_ctx *c, const uint8_t *frame, size_t pitch, int
   }
   const OrbGeom g = orb_geom(w, h, *ap);
   const bool blur = ap->blur_for_descriptor != 0;
-  AlignCarve cv;
-  const size_t need = align_carve(nullptr, g, blur, ap->nfeatures, cv);
+  const AlignCarve ac = align_carve(g, blur, g.kcap);
+  const size_t need = ac.bytes;
   if (need > c->align_bytes) {
     const tvl1_status r = arena_alloc(c, &c->align_scratch, &c->align_bytes, need, st);
     if (r != TVL1_OK) return r;
   }
-  align_carve(c->align_scratch, g, blur, ap->nfeatures, cv);
+  const AlignPtrs cv = align_ptrs(c->align_scratch, ac);
   OrbSet q;
   {
     const tvl1_status r = orb_detect(c, frame, pitch, g, *ap, cv, cv.desc[0], q, st, true);
@@ -2723,8 +2678,8 @@ tvl1_status tvl1_match_knn2(tvl1_ctx *c, const uint8_t *query, int32_t nq, const
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   order_streams(c, st);
-  const int nseg = std::max(1, std::min(kMatchSegs, (nt + 255) / 256));
-  const int seg = (int)align_up((size_t)((std::max(nt, 1) + nseg - 1) / nseg), 64);
+  const MatchPlan mp = match_plan(nt);
+  const int nseg = mp.nseg, seg = mp.seg;
   // scratch: query and train descriptors, the per-segment top-2, the merged top-2
   const size_t oq = 0, ot = align_up((size_t)nq * 32, 256);
   const size_t op = ot + align_up((size_t)std::max(nt, 1) * 32, 256);
@@ -2744,7 +2699,6 @@ tvl1_status tvl1_match_knn2(tvl1_ctx *c, const uint8_t *query, int32_t nq, const
   hipLaunchKernelGGL(ka_match2, dim3((nq + 63) / 64, nseg), dim3(64), 0, st, dq, nq, dt, nt, seg, part);
   hipLaunchKernelGGL(ka_match2_merge, dim3((nq + 255) / 256), dim3(256), 0, st, part, nq, nseg, best, dd);
   HIP_TRY(c, hipGetLastError());
-  static_assert(sizeof(int2) == 2 * sizeof(int32_t), "int2 layout");
   HIP_TRY(c, hipMemcpyAsync(idx, best, (size_t)nq * sizeof(int2), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(dist, dd, (size_t)nq * sizeof(int2), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));

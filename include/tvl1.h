@@ -249,7 +249,10 @@ tvl1_status tvl1_find_alignment(tvl1_ctx *ctx,
  * px, cv::KeyPoint::pt), octave (the pyramid level), angle (degrees in [0, 360)), response;
  * desc: 32 bytes per keypoint (rBRIEF, 256 bits, bit j of byte k = test 8k + j).  Host
  * outputs for up to cap keypoints; *n = how many were found (may exceed cap: the first cap
- * are written).  Synchronous on stream. */
+ * are written).  *n can exceed params->nfeatures: the budget is split over the levels by
+ * ORB's quota rule, each level's share rounded to an integer and the last level given the
+ * remainder if any, so the shares can add up to a few more (16 levels at scale 1.1 and
+ * nfeatures 16 give 17; 12 levels at 1.2 and 24 give 25).  Synchronous on stream. */
 tvl1_status tvl1_orb_detect(tvl1_ctx *ctx, const uint8_t *frame, size_t pitch, int32_t w,
                             int32_t h, const tvl1_align_params *params, float *kp,
                             uint8_t *desc, int32_t cap, int32_t *n, void *stream);

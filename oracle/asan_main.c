@@ -2,7 +2,10 @@
  * tests/test_host_hardening_cpu.py::test_oracle_under_asan).  Solves small synthetic pairs
  * at odd sizes through every code path of the restatement: both profiles, gamma, median,
  * fixed work, a pyramid that bottoms out, 1x1 / 16x16 edge sizes, and the seeded entry in
- * both arithmetics (a pitched seed whose taps leave the frame on every side). */
+ * both arithmetics (a pitched seed whose taps leave the frame on every side); and the
+ * pre-alignment restatement (tvl1_oracle_align.c) at its edges: frames with one candidate
+ * px and with none, a pitched view, a level quota sum above nfeatures, train sets of 0, 1
+ * and 65 descriptors, singular and far-off warps, and a pair of different sizes. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,6 +21,129 @@ static void pair(int w, int h, unsigned seed, uint8_t *a, uint8_t *b) {
       a[y * w + x] = (uint8_t)v;
       b[y * w + (x + 1) % w] = (uint8_t)(v + ((seed >> 8) & 3));
     }
+}
+
+/* a frame with corners everywhere: uniform noise from the same generator */
+static void noise(int w, int h, size_t pitch, unsigned seed, uint8_t *a) {
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) {
+      seed = seed * 1103515245u + 12345u;
+      a[(size_t)y * pitch + x] = (uint8_t)(seed >> 16);
+    }
+}
+
+static const tvl1_align_params kOrb = {5000, 1.2f, 8, 16, 0, 2, 31, 20, 0, 0.8f, 8, 5.0};
+
+/* orc_orb_detect into outputs of exactly cap rows; returns the count */
+static int detect(const uint8_t *img, size_t pitch, int w, int h, const tvl1_align_params *ap, int cap,
+                  uint8_t **desc_out) {
+  float *kp = malloc(sizeof(float) * 5 * (size_t)(cap > 0 ? cap : 1));
+  uint8_t *desc = malloc(32 * (size_t)(cap > 0 ? cap : 1));
+  const int n = orc_orb_detect(img, pitch, w, h, ap, kp, desc, cap);
+  free(kp);
+  if (desc_out)
+    *desc_out = desc;
+  else
+    free(desc);
+  return n;
+}
+
+static int align_paths(void) {
+  int fails = 0;
+  /* one candidate px, none, tile seams; a pitched view equals its packed copy */
+  static const int sizes[][2] = {{33, 33}, {32, 40}, {129, 97}};
+  for (size_t si = 0; si < sizeof sizes / sizeof sizes[0]; ++si) {
+    const int w = sizes[si][0], h = sizes[si][1];
+    const size_t pitch = (size_t)w + 71;
+    uint8_t *packed = malloc((size_t)w * h), *parent = malloc(pitch * (h + 8));
+    noise(w, h, (size_t)w, 3u + (unsigned)si, packed);
+    memset(parent, 0x55, pitch * (h + 8));
+    for (int y = 0; y < h; ++y) memcpy(parent + (size_t)(y + 5) * pitch + 3, packed + (size_t)y * w, w);
+    uint8_t *d0 = NULL, *d1 = NULL;
+    const int n0 = detect(packed, (size_t)w, w, h, &kOrb, 4096, &d0);
+    const int n1 = detect(parent + 5 * pitch + 3, pitch, w, h, &kOrb, 4096, &d1);
+    const int nshort = detect(packed, (size_t)w, w, h, &kOrb, n0 > 10 ? n0 - 10 : 0, NULL);
+    if (n0 < 0 || n0 != n1 || nshort != n0 || memcmp(d0, d1, 32 * (size_t)(n0 < 4096 ? n0 : 4096)) != 0 ||
+        (w == 32 && n0 != 0) || (w == 129 && n0 < 100)) {
+      fprintf(stderr, "orb %dx%d: %d packed, %d pitched, %d short\n", w, h, n0, n1, nshort);
+      ++fails;
+    }
+    /* the match list over train sets of 0, 1 and 65 descriptors */
+    if (w == 129) {
+      static const int nts[] = {0, 1, 65};
+      for (size_t k = 0; k < sizeof nts / sizeof nts[0]; ++k) {
+        const int nq = 3, nt = nts[k];
+        int32_t idx[6], dist[6];
+        orc_match_knn2(d0, nq, d0, nt, idx, dist);
+        const int want1 = nt > 1 ? 1 : 0;
+        for (int i = 0; i < nq; ++i)
+          if ((nt > i && (idx[2 * i] != i || dist[2 * i] != 0)) || (nt == 0 && idx[2 * i] != -1) ||
+              (idx[2 * i + 1] >= 0) != want1) {
+            fprintf(stderr, "match nt %d query %d: %d %d\n", nt, i, idx[2 * i], idx[2 * i + 1]);
+            ++fails;
+          }
+      }
+    }
+    free(d0);
+    free(d1);
+    free(packed);
+    free(parent);
+  }
+  /* 16 levels at 1.1 with 16 features: the level quotas add up to 17 */
+  {
+    const int w = 400, h = 300;
+    uint8_t *a = malloc((size_t)w * h);
+    noise(w, h, (size_t)w, 11u, a);
+    tvl1_align_params ap = kOrb;
+    ap.nlevels = 16, ap.scale_factor = 1.1f, ap.nfeatures = 16;
+    const int n = detect(a, (size_t)w, w, h, &ap, 17, NULL);
+    float aff[6];
+    int ng = -1, oc = -1;
+    const int rc = orc_find_alignment(a, (size_t)w, w, h, a, (size_t)w, w, h, &ap, aff, &ng, &oc);
+    if (n != 17 || rc != 0 || ng != 16) {
+      fprintf(stderr, "budget: %d keypoints, status %d, %d good, outcome %d\n", n, rc, ng, oc);
+      ++fails;
+    }
+    free(a);
+  }
+  /* singular (every px samples src(0, 0)) and far-off (all zero) warps, pitched planes */
+  {
+    enum { SW = 33, SH = 9, SP = 40, DW = 65, DH = 5, DP = 70 };
+    uint8_t src[SH * SP], dst[DH * DP];
+    noise(SW, SH, SP, 5u, src);
+    static const float Ms[3][6] = {{1, 2, 3, 2, 4, -1}, {1, 0, 1e6f, 0, 1, 1e6f}, {1, 0, -1e6f, 0, 1, -1e6f}};
+    for (int k = 0; k < 3; ++k) {
+      memset(dst, 0xA5, sizeof dst);
+      orc_warp_affine_u8(src, SP, SW, SH, dst, DP, DW, DH, Ms[k]);
+      for (int y = 0; y < DH; ++y)
+        for (int x = 0; x < DP; ++x) {
+          const int want = x >= DW ? 0xA5 : (k == 0 ? src[0] : 0);
+          if (dst[y * DP + x] != want) {
+            fprintf(stderr, "warp %d at (%d, %d): %d\n", k, x, y, dst[y * DP + x]);
+            ++fails;
+            y = DH;
+            break;
+          }
+        }
+    }
+  }
+  /* frame1 200 x 160 against frame0 260 x 190 and the other way round, pitched crops of one
+   * noise field 14 px and 9 px apart */
+  {
+    enum { BW = 300, BH = 220 };
+    uint8_t *base = malloc(BW * BH);
+    noise(BW, BH, BW, 21u, base);
+    float aff[6];
+    int ng = -1, oc = -1;
+    const int rc = orc_find_alignment(base + 9 * BW + 14, BW, 200, 160, base, BW, 260, 190, &kOrb, aff, &ng, &oc);
+    const int rs = orc_find_alignment(base, BW, 260, 190, base + 9 * BW + 14, BW, 200, 160, &kOrb, aff, &ng, &oc);
+    if (rc != 0 || rs != 0 || oc != 0 || ng <= 10) {
+      fprintf(stderr, "find_alignment: status %d / %d, %d good, outcome %d\n", rc, rs, ng, oc);
+      ++fails;
+    }
+    free(base);
+  }
+  return fails;
 }
 
 int main(void) {
@@ -79,6 +205,7 @@ int main(void) {
     free(u);
     free(v);
   }
+  fails += align_paths();
   printf("oracle asan driver: %d failures\n", fails);
   return fails != 0;
 }
