@@ -36,6 +36,13 @@
 //     stats_json's "initial_flow_auto" carries sad / count, the summed and counted absolute
 //     differences over the overlap at the estimate, and sad_zero / count_zero, the same at
 //     (0, 0); a drift outside the search range shows as two means that barely differ);
+//     "seededStripBatch" (default false: a seeded pair leaves the strip batch and its ROIs are
+//     solved one by one; true: a pair the *global* "useInitialFlow" / "initialFlow" seeds stays
+//     in its tvl1_calc_batch chunk -- a numeric seed through tvl1_calc_batch_const_init,
+//     "auto" through tvl1_calc_batch_auto_init on the packed strips of each ROI key, with the
+//     per-pair path's range min(initialFlowMaxShift, 128, min(W, h) / 4), below 1 unseeded --
+//     with the same flows, outputs and stats_json entries; per-image seed keys still send a
+//     pair the per-pair way);
 //   * "style": 2 (from_list below): the average-flow alignment of a slice list that the
 //     reference declares and keeps disabled; keys "slices" | "file_list", "border",
 //     "save_flow" (DESIGN 11, and 8 for where it departs from the disabled code).
@@ -1222,7 +1229,8 @@ static int from_file(Value &args, bool plan_only) {
           pl["features"] = resolve_features(im, args);
           pl["strip_batch"] = (bool)batch_ok[i];   // solved in a tvl1_calc_batch chunk
           if (const InitFlow f0 = initial_flow_of(im, args); f0.automatic) {
-            pl["initialFlow"] = "auto";   // tvl1_estimate_shift, then tvl1_calc_init, per ROI
+            pl["initialFlow"] = "auto";   // tvl1_estimate_shift, then tvl1_calc_init, per ROI (or,
+                                          // strip_batch: tvl1_calc_batch_auto_init per ROI key)
             pl["initialFlowMaxShift"] = f0.max_shift;
           } else if (f0.on) {   // tvl1_calc_init per ROI
             pl["initialFlow"][0] = (double)f0.dx;
@@ -1341,6 +1349,8 @@ static int from_file(Value &args, bool plan_only) {
     const tvl1_params prm = generate_TV_args(Value(), args);
     const std::string otype = output_type_of(Value(), args);
     const int mode = otype == "map" ? 1 : 0;   // no features on this path
+    // "seededStripBatch": the global seed of every pair of the batch (else none is seeded)
+    const InitFlow ginit = initial_flow_of(Value(), args);
     // device buffers (grown): the chunk's packed frames and flows of one ROI key
     uint8_t *dP = nullptr, *dQ = nullptr;
     float *dU = nullptr, *dV = nullptr;
@@ -1527,8 +1537,29 @@ static int from_file(Value &args, bool plan_only) {
               }));
           }
           const auto t0 = std::chrono::steady_clock::now();
-          tvl1_status sc = tvl1_calc_batch(dc.ctx, nb, dP, W, px, dQ, W, px, W, h, dU, dV, 4 * (size_t)W,
-                                           4 * px, st.data(), dc.stream);
+          // the chunk's seed, as solve_wrapper's per ROI: a constant, or each strip's drift
+          // within auto_R on the packed strips (too small to search: unseeded)
+          bool seeded = ginit.on;
+          int auto_R = 0;
+          std::vector<tvl1_shift> shifts;
+          std::vector<float> seed_xy;
+          if (ginit.automatic) {
+            auto_R = std::max(0, std::min(std::min(ginit.max_shift, 128), std::min(W, h) / 4));
+            seeded = auto_R >= 1;
+            if (seeded) shifts.resize(nb);
+          } else if (seeded) {
+            for (int b = 0; b < nb; ++b) seed_xy.push_back(ginit.dx), seed_xy.push_back(ginit.dy);
+          }
+          tvl1_status sc;
+          if (!seeded)
+            sc = tvl1_calc_batch(dc.ctx, nb, dP, W, px, dQ, W, px, W, h, dU, dV, 4 * (size_t)W, 4 * px,
+                                 st.data(), dc.stream);
+          else if (ginit.automatic)
+            sc = tvl1_calc_batch_auto_init(dc.ctx, nb, dP, W, px, dQ, W, px, W, h, auto_R, shifts.data(),
+                                           dU, dV, 4 * (size_t)W, 4 * px, st.data(), dc.stream);
+          else
+            sc = tvl1_calc_batch_const_init(dc.ctx, nb, dP, W, px, dQ, W, px, W, h, seed_xy.data(), dU,
+                                            dV, 4 * (size_t)W, 4 * px, st.data(), dc.stream);
           if (sc == TVL1_OK)
             sc = tvl1_postprocess_batch(dc.ctx, nb, dU, dV, 4 * (size_t)W, 4 * px, dQ, W, px, W, h,
                                         mode, dc.stream);
@@ -1589,6 +1620,19 @@ static int from_file(Value &args, bool plan_only) {
             const size_t nw = std::min((size_t)st[b].warp_iterations_capacity,
                                        (size_t)std::max(0, st[b].levels) * std::max(1, prm.warps));
             for (size_t k = 0; k < nw; ++k) sv["warp_iterations"][(int)k] = st[b].warp_iterations[k];
+            if (seeded) {
+              sv["initial_flow"][0] = ginit.automatic ? (double)(float)shifts[b].dx : (double)ginit.dx;
+              sv["initial_flow"][1] = ginit.automatic ? (double)(float)shifts[b].dy : (double)ginit.dy;
+            }
+            if (ginit.automatic) {
+              sv["initial_flow_auto"]["max_shift"] = auto_R;
+              if (auto_R) {
+                sv["initial_flow_auto"]["sad"] = (int64_t)shifts[b].sad;
+                sv["initial_flow_auto"]["count"] = (int64_t)shifts[b].count;
+                sv["initial_flow_auto"]["sad_zero"] = (int64_t)shifts[b].sad_zero;
+                sv["initial_flow_auto"]["count_zero"] = (int64_t)shifts[b].count_zero;
+              }
+            }
             sv["read_rows_only"] = items[b].p->partial && items[b].q->partial;
             solves[b].push_back(sv);
             if (sampled) {
@@ -1701,9 +1745,12 @@ static int from_file(Value &args, bool plan_only) {
   // build-only "strip_batch": strip pairs per tvl1_calc_batch (default 256; 0 or 1 = one
   // tvl1_calc per strip, the r3 path).  A pair is batched when the job's ROIs are all top /
   // bottom and its own keys are only the production ones (gen_cross_file_list.py:47-54);
-  // features, per-image ROIs / scales / TV parameters go the per-pair way.
+  // features, per-image ROIs / scales / TV parameters go the per-pair way.  So does a seeded
+  // pair, unless "seededStripBatch" keeps the pairs the global config seeds in the batch
+  // (per-image seed keys are not production keys).
   const int strip_batch = std::min(256, std::max(0, args.get("strip_batch", 256).asInt()));
   const std::string gotype = output_type_of(Value(), args);
+  const bool seeded_batch = args.get("seededStripBatch", false).asBool();
   const bool batching = strip_job && strip_batch > 1 && !resolve_features(Value(), args) &&
                         (gotype == "map" || gotype == "flow" || gotype == "random_points");
   if (batching) {
@@ -1712,8 +1759,8 @@ static int from_file(Value &args, bool plan_only) {
     roi_bottom = args["rois"].get("bottom", 300).asInt();
     static const char *kProd[] = {"p", "q", "pId", "qId", "pGroupId", "qGroupId", "output_name", "output"};
     for (size_t i = 0; i < n; ++i) {
-      // a seeded pair's ROIs are solved one by one (tvl1_calc_init)
-      bool ok = images[i].isObject() && !initial_flow_of(images[i], args).on;
+      // a seeded pair's ROIs are solved one by one (tvl1_calc_init), or "seededStripBatch"
+      bool ok = images[i].isObject() && (seeded_batch || !initial_flow_of(images[i], args).on);
       for (auto &k : images[i].memberNames())
         ok = ok && std::find_if(std::begin(kProd), std::end(kProd), [&](const char *x) { return k == x; }) !=
                        std::end(kProd);

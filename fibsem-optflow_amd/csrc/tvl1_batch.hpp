@@ -99,6 +99,70 @@ TVL1_PLAIN __global__ void kb_flow_copy(const float *__restrict__ s1, const floa
   dst[(size_t)y * dp + x] = src[(size_t)y * sp + x];
 }
 
+// resize_px<C> of a plane that holds the constant c everywhere: the same source coordinates
+// and tap weights, and the same four accumulations from out = 0 with t00 = t01 = t10 = t11 =
+// c.  The weights depend on the px (ax + bx is 1 only before rounding), so the result is not
+// one value per plane.  resize_px's clamps of the +1 taps only choose which source px is
+// read -- every one of them is c -- and the weights take the unclamped x2 / y2, so the source
+// size does not enter.
+template <bool C>
+__device__ __forceinline__ float resize_const_px(float c, int dx, int dy, float fx, float fy) {
+  const float dxf = (float)dx, dyf = (float)dy;
+  const float src_x = dxf * fx;
+  const float src_y = dyf * fy;
+  const int x1 = (int)floorf(src_x);
+  const int y1 = (int)floorf(src_y);
+  const int x2 = x1 + 1;
+  const int y2 = y1 + 1;
+  const float ax = C ? __builtin_fmaf(-dxf, fx, (float)x2) : (float)x2 - src_x;
+  const float bx = C ? __builtin_fmaf(dxf, fx, -(float)x1) : src_x - (float)x1;
+  const float ay = C ? __builtin_fmaf(-dyf, fy, (float)y2) : (float)y2 - src_y;
+  const float by = C ? __builtin_fmaf(dyf, fy, -(float)y1) : src_y - (float)y1;
+  float out = 0.0f;
+  if (C) {
+    out = __builtin_fmaf(c, ax * ay, out);
+    out = __builtin_fmaf(c, bx * ay, out);
+    out = __builtin_fmaf(c, ax * by, out);
+    out = __builtin_fmaf(c, bx * by, out);
+  } else {
+    out = out + c * (ax * ay);
+    out = out + c * (bx * ay);
+    out = out + c * (ax * by);
+    out = out + c * (bx * by);
+  }
+  return out;
+}
+
+// [A.2b] The first kb_flow_down step of pairs whose seed is one constant per component
+// (tvl1_calc_batch_const_init, tvl1_calc_batch_auto_init): level 1 of pair b, component k
+// (blockIdx.z = 2 * b + k) from a level-0 plane that holds seed[2 * b + k] everywhere and
+// exists nowhere -- the kernel reads that one float per block and writes the level.  (The
+// index is blockIdx.z itself, uniform as it is: the constant arrives by a scalar load.)
+template <bool C>
+__global__ void kb_flow_down_const(const float *__restrict__ seed, float *__restrict__ d1,
+                                   float *__restrict__ d2, int dw, int dh, int dp, size_t dps,
+                                   float fx, float fy, float mul) {
+  const int x = blockIdx.x * 64 + threadIdx.x;
+  const int y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= dw || y >= dh) return;
+  const int b = blockIdx.z >> 1;
+  const float c = seed[blockIdx.z];
+  float *dst = ((blockIdx.z & 1) == 0 ? d1 : d2) + b * dps;
+  dst[(size_t)y * dp + x] = resize_const_px<C>(c, x, y, fx, fy) * mul;
+}
+
+// kb_flow_copy from such a seed: a one-level pyramid starts from the constants themselves
+// (and a pair solved alone takes its constant as two planes filled by this kernel).
+TVL1_PLAIN __global__ void kb_flow_fill(const float *__restrict__ seed, float *__restrict__ d1,
+                                        float *__restrict__ d2, int W, int H, int dp, size_t dps) {
+  const int x = blockIdx.x * 64 + threadIdx.x;
+  const int y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= W || y >= H) return;
+  const int b = blockIdx.z >> 1;
+  float *dst = ((blockIdx.z & 1) == 0 ? d1 : d2) + b * dps;
+  dst[(size_t)y * dp + x] = seed[blockIdx.z];
+}
+
 // K5 as k_warp_ring's streaming gather (64-px bands, LDS window ring of I1 / I1x / I1y
 // built from I1) on each selected pair (blockIdx.y = entry of sel).
 struct BatchRing {

@@ -188,6 +188,8 @@ struct tvl1_ctx {
   int4 *align_pat = nullptr;            // the rBRIEF pair pattern (device, set once)
   char *shift_scratch = nullptr;        // tvl1_estimate_shift's pyramids, tables and records
   size_t shift_bytes = 0;
+  char *seed_scratch = nullptr;         // tvl1_calc_batch_const_init / _auto_init: every pair's
+  size_t seed_bytes = 0;                // constants (then two planes for pairs solved alone)
   int bnblk = 0;                        // partials per pair
   int check = 0;             // TVL1_CHECK=1: synchronise + check after every launch (diagnostics)
 
@@ -706,9 +708,12 @@ struct Frames {
 
 // The initial flow of a solve (tvl1_calc_init): device planes of the frame's
 // size, row pitch and pair stride in floats (stride 0: one seed for every pair of a batch).
+// A batch may instead be seeded by one constant per pair and component (cst: device, pair b's
+// at cst[2 b], cst[2 b + 1]; the planes exist nowhere then and u0 = v0 = NULL).
 struct Seed {
   const float *u0, *v0;
   size_t pitch, stride;
+  const float *cst;
 };
 
 // [A.1] I0f = convertTo(CV_32F, u8 ? 1 : 255) into the level-0 planes
@@ -1517,13 +1522,29 @@ static tvl1_status batch_initial_flow(tvl1_ctx *c, int n, const Seed *seed, int 
   const bool contract = contracts(math_of(c->prm));
   const size_t tkf = prof_begin(c, st);
   double fb = 0.0;
-  if (L == 1) {
+  if (L == 1 && seed->cst) {
+    hipLaunchKernelGGL(kb_flow_fill, grid2(W, H, 2 * n), kBlk2, 0, st, seed->cst, c->bU[0][0],
+                       c->bU[0][1], W, H, g.ps[0], ps);
+    fb = (double)n * W * H * 8.0;
+  } else if (L == 1) {
     hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2 * n), kBlk2, 0, st, seed->u0, seed->v0,
                        (int)seed->pitch, seed->stride, c->bU[0][0], c->bU[0][1], W, H, g.ps[0], ps);
     fb = (double)n * W * H * 16.0;
   }
   int set = L & 1;   // L - 1 steps end in set 0
   for (int s = 1; s < L; ++s, set ^= 1) {
+    if (s == 1 && seed->cst) {   // per-pair constants: level 1 from a level 0 that is not stored
+      if (contract)
+        hipLaunchKernelGGL(kb_flow_down_const<true>, grid2(g.ws[1], g.hs[1], 2 * n), kBlk2, 0, st,
+                           seed->cst, c->bU[set][0], c->bU[set][1], g.ws[1], g.hs[1], g.ps[1], ps,
+                           fdown, fdown, fmul);
+      else
+        hipLaunchKernelGGL(kb_flow_down_const<false>, grid2(g.ws[1], g.hs[1], 2 * n), kBlk2, 0, st,
+                           seed->cst, c->bU[set][0], c->bU[set][1], g.ws[1], g.hs[1], g.ps[1], ps,
+                           fdown, fdown, fmul);
+      fb += (double)n * g.ws[1] * g.hs[1] * 8;
+      continue;
+    }
     const float *s1 = s == 1 ? seed->u0 : c->bU[set ^ 1][0], *s2 = s == 1 ? seed->v0 : c->bU[set ^ 1][1];
     const int sp = s == 1 ? (int)seed->pitch : g.ps[s - 1];
     const size_t sps = s == 1 ? seed->stride : ps;
@@ -2367,7 +2388,7 @@ tvl1_status tvl1_calc_init(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const 
   HIP_TRY(c, hipSetDevice(c->device));
   s = ensure_geometry(c, W, H, (hipStream_t)stream);
   if (s != TVL1_OK) return s;
-  const Seed seed{u0, v0, init_pitch / sizeof(float), 0};
+  const Seed seed{u0, v0, init_pitch / sizeof(float), 0, nullptr};
   return solve(c, Frames{I0, I1, pitch0, pitch1, false}, &seed, W, H, u, v, fpitch, stats,
                (hipStream_t)stream);
 }
@@ -2409,12 +2430,11 @@ tvl1_status tvl1_calc_f32(tvl1_ctx *c, const float *I0, size_t pitch0, const flo
 }
 
 
-// tvl1_calc_batch (seed null) and tvl1_calc_batch_init (seed of pair 0, stride to the next)
-static tvl1_status calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
-                              size_t pair_stride0, const uint8_t *I1, size_t pitch1,
-                              size_t pair_stride1, const Seed *seed, int32_t W, int32_t H,
-                              float *u, float *v, size_t fpitch, size_t flow_pair_stride,
-                              tvl1_stats *stats, void *stream) {
+// The arguments of the tvl1_calc_batch* calls, checked before anything is launched
+static tvl1_status check_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                               size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                               size_t pair_stride1, int32_t W, int32_t H, float *u, float *v,
+                               size_t fpitch, size_t flow_pair_stride) {
   if (n <= 0) return set_err(c, TVL1_EINVAL, "batch size must be > 0 (got %d)", n);
   tvl1_status s = check_call(c, I0, pitch0, I1, pitch1, W, H, u, v, fpitch);
   if (s != TVL1_OK) return s;
@@ -2423,27 +2443,41 @@ static tvl1_status calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t 
                 (pair_stride1 != 0 && pair_stride1 < pitch1 * (size_t)H) ||
                 flow_pair_stride < fpitch * (size_t)H))
     return set_err(c, TVL1_EINVAL, "pair strides must be 0 or cover one image; the flow stride one field");
-  HIP_TRY(c, hipSetDevice(c->device));
-  s = ensure_geometry(c, W, H, (hipStream_t)stream);
-  if (s != TVL1_OK) return s;
+  return TVL1_OK;
+}
+
+// The most pairs the batched kernels take in one chunk of the ctx's geometry (ensure_geometry
+// ran), or 0: the pairs are solved one by one
+static int batch_chunk_max(const tvl1_ctx *c, int H) {
   const tvl1_params &prm = c->prm;
   const float taut = (float)(prm.tau / prm.theta);
   // the batched kernels cover the reference's path with gamma = 0 (every production
   // config); other parameter sets solve the pairs one by one, same results
-  bool batched = prm.profile == 0 && prm.gamma == 0.0 && taut >= 0.0f && taut <= FLT_MAX;
+  if (!(prm.profile == 0 && prm.gamma == 0.0 && taut >= 0.0f && taut <= FLT_MAX)) return 0;
+  // the batched passes address the 4 p planes of every pair of a chunk through one buffer
+  // descriptor (RollBufs): that group must stay below 2 GiB
+  const double pplane = (double)align_up((size_t)c->geo.ps[0] * H, 64) * sizeof(float);
+  const int nmax = (int)((double)(((size_t)1 << 31) - 8192) / (4.0 * pplane));
+  // (nmax < 1: frames this large solve one by one, tvl1_calc's fallbacks)
+  return std::min(kBatchMax, std::max(nmax, 0));
+}
+
+// tvl1_calc_batch (seed null) and tvl1_calc_batch_init (seed of pair 0, stride to the next)
+static tvl1_status calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                              size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                              size_t pair_stride1, const Seed *seed, int32_t W, int32_t H,
+                              float *u, float *v, size_t fpitch, size_t flow_pair_stride,
+                              tvl1_stats *stats, void *stream) {
+  tvl1_status s = check_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, W, H, u, v,
+                              fpitch, flow_pair_stride);
+  if (s != TVL1_OK) return s;
+  HIP_TRY(c, hipSetDevice(c->device));
+  s = ensure_geometry(c, W, H, (hipStream_t)stream);
+  if (s != TVL1_OK) return s;
   // chunk size: kBatchMax pairs, fewer when their batch arena would not fit in half of
   // the device memory free now (large frames: one chunk of 256 6144x4096 pairs is 0.7 TB)
-  int chunk = kBatchMax;
-  if (batched) {
-    // the batched passes address the 4 p planes of every pair of a chunk through one buffer
-    // descriptor (RollBufs): that group must stay below 2 GiB
-    const double pplane = (double)align_up((size_t)c->geo.ps[0] * H, 64) * sizeof(float);
-    const int nmax = (int)((double)(((size_t)1 << 31) - 8192) / (4.0 * pplane));
-    if (nmax < 1)
-      batched = false;   // frames this large solve one by one (tvl1_calc's fallbacks)
-    else
-      chunk = std::min(chunk, nmax);
-  }
+  int chunk = batch_chunk_max(c, H);
+  const bool batched = chunk > 0;
   if (batched) {
     const Geometry &g = c->geo;
     double per_pair = 15.0 * align_up((size_t)g.ps[0] * H, 64) * sizeof(float);
@@ -2463,8 +2497,20 @@ static tvl1_status calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t 
     float *ub = reinterpret_cast<float *>(reinterpret_cast<char *>(u) + (size_t)b0 * flow_pair_stride);
     float *vb = reinterpret_cast<float *>(reinterpret_cast<char *>(v) + (size_t)b0 * flow_pair_stride);
     Seed sb{};
-    if (seed) sb = Seed{seed->u0 + (size_t)b0 * seed->stride, seed->v0 + (size_t)b0 * seed->stride,
-                        seed->pitch, seed->stride};
+    if (seed && seed->cst) {
+      // constants: the chunk's first pair's; a pair solved alone takes the two planes behind
+      // the constants (calc_batch_const), filled here, as tvl1_calc_init's seed
+      sb = Seed{nullptr, nullptr, 0, 0, seed->cst + 2 * (size_t)b0};
+      if (!batched) {
+        hipLaunchKernelGGL(kb_flow_fill, grid2(W, H, 2), kBlk2, 0, (hipStream_t)stream, sb.cst,
+                           const_cast<float *>(seed->u0), const_cast<float *>(seed->v0), W, H, W,
+                           (size_t)0);
+        sb = Seed{seed->u0, seed->v0, (size_t)W, 0, nullptr};
+      }
+    } else if (seed) {
+      sb = Seed{seed->u0 + (size_t)b0 * seed->stride, seed->v0 + (size_t)b0 * seed->stride,
+                seed->pitch, seed->stride, nullptr};
+    }
     const Seed *sd = seed ? &sb : nullptr;
     s = batched ? solve_batch_chunk(c, m, i0, pitch0, pair_stride0, i1, pitch1, pair_stride1, sd, W,
                                     H, ub, vb, fpitch, flow_pair_stride, stats ? stats + b0 : nullptr,
@@ -2501,7 +2547,7 @@ tvl1_status tvl1_calc_batch_init(tvl1_ctx *c, int32_t n, const uint8_t *I0, size
   if (init_pair_stride % sizeof(float) ||
       (n > 1 && H > 0 && init_pair_stride != 0 && init_pair_stride < init_pitch * (size_t)H))
     return set_err(c, TVL1_EINVAL, "initial flow pair stride must be 0 or cover one field, in whole floats");
-  const Seed seed{u0, v0, init_pitch / sizeof(float), init_pair_stride / sizeof(float)};
+  const Seed seed{u0, v0, init_pitch / sizeof(float), init_pair_stride / sizeof(float), nullptr};
   return calc_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, &seed, W, H, u, v,
                     fpitch, flow_pair_stride, stats, stream);
 }
@@ -2929,7 +2975,7 @@ tvl1_status tvl1_sad_shifts_u8(tvl1_ctx *c, const uint8_t *I0, size_t p0, const 
 // One chunk of pairs: pyramid, then per level table and selection, all enqueued on st
 static tvl1_status shift_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size_t p0, size_t s0,
                                const uint8_t *I1, size_t p1, size_t s1, int w, int h, int R,
-                               tvl1_shift *out, hipStream_t st) {
+                               tvl1_shift *out, float *seed_out, hipStream_t st) {
   int L = 0;
   while (((R + (1 << L) - 1) >> L) > kShiftMaxR) ++L;
   int ws[kShiftLevels], hs[kShiftLevels];
@@ -2982,14 +3028,19 @@ static tvl1_status shift_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size_t p0,
                    l > 0 ? bases + (size_t)(l - 1) * n : nullptr, recs};
     hipLaunchKernelGGL(k_shift_select, dim3(1, (unsigned)n), dim3(64), 0, st, b);
   }
+  // a seeded batch takes its constants from the records here, before the next chunk (or the
+  // next call) re-lays the workspace
+  if (seed_out)
+    hipLaunchKernelGGL(k_shift_seed, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, recs, n, seed_out);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, recs, (size_t)n * sizeof(tvl1_shift), hipMemcpyDeviceToHost, st));
   return TVL1_OK;
 }
 
-tvl1_status tvl1_estimate_shift_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t p0, size_t s0,
-                                      const uint8_t *I1, size_t p1, size_t s1, int32_t w, int32_t h,
-                                      int32_t R, tvl1_shift *out, void *stream) {
+// The arguments of tvl1_estimate_shift_batch, checked before anything is launched
+static tvl1_status check_shift_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t p0, size_t s0,
+                                     const uint8_t *I1, size_t p1, size_t s1, int32_t w, int32_t h,
+                                     int32_t R, const tvl1_shift *out) {
   tvl1_status s = check_shift_frames(c, I0, p0, I1, p1, w, h, out);
   if (s != TVL1_OK) return s;
   if (n < 1) return set_err(c, TVL1_EINVAL, "n must be >= 1 (got %d)", n);
@@ -2998,16 +3049,102 @@ tvl1_status tvl1_estimate_shift_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0,
     return set_err(c, TVL1_EINVAL, "4 * max_shift = %d above min(w, h) = %d", 4 * R, std::min(w, h));
   if (n > 1 && ((s0 != 0 && s0 < p0 * (size_t)(h - 1) + w) || (s1 != 0 && s1 < p1 * (size_t)(h - 1) + w)))
     return set_err(c, TVL1_EINVAL, "pair_stride0 / pair_stride1 must be 0 or cover one image");
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
+  return TVL1_OK;
+}
+
+// The estimate of n pairs enqueued on st, kShiftChunk at a time: records to out (host), and,
+// for a seeded batch, every pair's constants to seed_out (device, 2 n floats)
+static tvl1_status shift_chunks(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t p0, size_t s0,
+                                const uint8_t *I1, size_t p1, size_t s1, int32_t w, int32_t h,
+                                int32_t R, tvl1_shift *out, float *seed_out, hipStream_t st) {
   for (int32_t b = 0; b < n; b += kShiftChunk) {
     // the next chunk re-lays the workspace: in stream order behind this one's record copy
     const int m = std::min(kShiftChunk, n - b);
     TVL1_TRY(shift_chunk(c, m, I0 + (size_t)b * s0, p0, s0, I1 + (size_t)b * s1, p1, s1, w, h, R,
-                         out + b, st));
+                         out + b, seed_out ? seed_out + 2 * (size_t)b : nullptr, st));
   }
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_estimate_shift_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t p0, size_t s0,
+                                      const uint8_t *I1, size_t p1, size_t s1, int32_t w, int32_t h,
+                                      int32_t R, tvl1_shift *out, void *stream) {
+  tvl1_status s = check_shift_batch(c, n, I0, p0, s0, I1, p1, s1, w, h, R, out);
+  if (s != TVL1_OK) return s;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  TVL1_TRY(shift_chunks(c, n, I0, p0, s0, I1, p1, s1, w, h, R, out, nullptr, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   return TVL1_OK;
+}
+
+// ---- Batched solves seeded by one constant per pair (added under ABI 9) ----
+// seed_xy (host, 2 n floats) or, when it is NULL, the drift estimate of every pair (records to
+// shifts): the constants go to a block of their own, which lives through every chunk of the
+// solve -- the shift workspace is re-laid per 256 pairs, the batch arena per chunk
+static tvl1_status calc_batch_const(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                                    size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                                    size_t pair_stride1, int32_t W, int32_t H, const float *seed_xy,
+                                    int32_t R, tvl1_shift *shifts, float *u, float *v,
+                                    size_t fpitch, size_t flow_pair_stride, tvl1_stats *stats,
+                                    void *stream) {
+  tvl1_status s = check_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, W, H, u, v,
+                              fpitch, flow_pair_stride);
+  if (s != TVL1_OK) return s;
+  if (c->prm.profile == 1)
+    return set_err(c, TVL1_EINVAL, "profile 1 takes no initial flow (tvl1_calc_init)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  s = ensure_geometry(c, W, H, st);
+  if (s != TVL1_OK) return s;
+  // pairs solved one by one (gamma != 0) take their constant as planes, one pair's at a time
+  const size_t cst_b = align_up((size_t)2 * n * sizeof(float), 256);
+  const size_t plane_b = batch_chunk_max(c, H) > 0 ? 0 : align_up((size_t)W * H * sizeof(float), 256);
+  if (cst_b + 2 * plane_b > c->seed_bytes)
+    TVL1_TRY(arena_alloc(c, &c->seed_scratch, &c->seed_bytes,
+                         std::max<size_t>(cst_b + 2 * plane_b, 64 << 10), st));
+  float *cst = reinterpret_cast<float *>(c->seed_scratch);
+  if (seed_xy)
+    HIP_TRY(c, hipMemcpyAsync(cst, seed_xy, (size_t)2 * n * sizeof(float), hipMemcpyHostToDevice, st));
+  else
+    TVL1_TRY(shift_chunks(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, W, H, R, shifts,
+                          cst, st));
+  const Seed seed{plane_b ? reinterpret_cast<float *>(c->seed_scratch + cst_b) : nullptr,
+                  plane_b ? reinterpret_cast<float *>(c->seed_scratch + cst_b + plane_b) : nullptr,
+                  (size_t)W, 0, cst};
+  s = calc_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, &seed, W, H, u, v, fpitch,
+                 flow_pair_stride, stats, stream);
+  if (s != TVL1_OK) return s;
+  // the records are on the host when the call returns (the solve has waited at its residual
+  // checks: this wait is for its last launches)
+  if (!seed_xy) HIP_TRY(c, hipStreamSynchronize(st));
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_calc_batch_const_init(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                                       size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                                       size_t pair_stride1, int32_t W, int32_t H,
+                                       const float *seed_xy, float *u, float *v, size_t fpitch,
+                                       size_t flow_pair_stride, tvl1_stats *stats, void *stream) {
+  if (!seed_xy) return set_err(c, TVL1_EINVAL, "null initial flow constants");
+  for (int64_t i = 0; i < 2 * (int64_t)std::max(n, 0); ++i)
+    if (!std::isfinite(seed_xy[i]))
+      return set_err(c, TVL1_EINVAL, "initial flow constant %lld of pair %lld is not finite",
+                     (long long)(i & 1), (long long)(i >> 1));
+  return calc_batch_const(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, W, H, seed_xy, 0,
+                          nullptr, u, v, fpitch, flow_pair_stride, stats, stream);
+}
+
+tvl1_status tvl1_calc_batch_auto_init(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                                      size_t pair_stride0, const uint8_t *I1, size_t pitch1,
+                                      size_t pair_stride1, int32_t W, int32_t H, int32_t max_shift,
+                                      tvl1_shift *shifts, float *u, float *v, size_t fpitch,
+                                      size_t flow_pair_stride, tvl1_stats *stats, void *stream) {
+  const tvl1_status s = check_shift_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, W,
+                                          H, max_shift, shifts);
+  if (s != TVL1_OK) return s;
+  return calc_batch_const(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, W, H, nullptr,
+                          max_shift, shifts, u, v, fpitch, flow_pair_stride, stats, stream);
 }
 
 tvl1_status tvl1_estimate_shift(tvl1_ctx *c, const uint8_t *I0, size_t p0, const uint8_t *I1, size_t p1,
@@ -3159,6 +3296,7 @@ void tvl1_destroy(tvl1_ctx *c) {
   if (c->gather_scratch) (void)hipFree(c->gather_scratch);
   if (c->small_scratch) (void)hipFree(c->small_scratch);
   if (c->shift_scratch) (void)hipFree(c->shift_scratch);
+  if (c->seed_scratch) (void)hipFree(c->seed_scratch);
   for (auto &r : c->retired) free_retired(r);
   if (c->align_pat) (void)hipFree(c->align_pat);
   if (c->pinned) (void)hipHostFree(c->pinned);

@@ -332,4 +332,14 @@ __global__ __launch_bounds__(64) void k_shift_select(ShiftSelArgs a) {
   }
 }
 
+// The hand-over to a seeded batch (tvl1_calc_batch_auto_init): the level-0 records of n pairs
+// as kb_flow_down_const's per-pair constants, seed[2 b] = (float)dx_b, seed[2 b + 1] =
+// (float)dy_b, read where k_shift_select left them (no host read between estimate and solve).
+__global__ void k_shift_seed(const tvl1_shift *__restrict__ recs, int n, float *__restrict__ seed) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= n) return;
+  seed[2 * b] = (float)recs[b].dx;
+  seed[2 * b + 1] = (float)recs[b].dy;
+}
+
 }  // namespace tvl1k

@@ -272,6 +272,20 @@ def load_engine() -> C.CDLL:
                                               C.c_int32, C.c_int32, C.c_int32,
                                               C.POINTER(TVL1Shift), C.c_void_p]
     lib.tvl1_estimate_shift_batch.restype = C.c_int
+    # batched solves seeded by one constant per pair (added under ABI 9)
+    lib.tvl1_calc_batch_const_init.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                                               C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                               C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                               C.POINTER(TVL1Stats), C.c_void_p]
+    lib.tvl1_calc_batch_const_init.restype = C.c_int
+    lib.tvl1_calc_batch_auto_init.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_int32, C.c_int32, C.c_int32,
+                                              C.POINTER(TVL1Shift), C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_size_t, C.POINTER(TVL1Stats),
+                                              C.c_void_p]
+    lib.tvl1_calc_batch_auto_init.restype = C.c_int
     lib.tvl1_sad_shifts_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p]
@@ -412,11 +426,21 @@ class Engine:
     def calc_batch_device(self, n: int, dI0: int, pitch0: int, stride0: int, dI1: int,
                           pitch1: int, stride1: int, w: int, h: int, du: int, dv: int,
                           flow_pitch: int, flow_stride: int, stream: int = 0,
-                          warp_iters: bool = False, init=None):
+                          warp_iters: bool = False, init=None, init_const=None,
+                          auto_shift=None):
         """tvl1_calc_batch on device buffers: n pairs of one size, pair b at base + b*stride
         (bytes).  Returns one stats dict per pair (+ per-warp iterations if asked).  init =
         (du0, dv0[, pitch[, stride]]): tvl1_calc_batch_init from those flows (device pointers;
-        bytes, default 4 * w and pitch * h; stride 0 = one seed for every pair)."""
+        bytes, default 4 * w and pitch * h; stride 0 = one seed for every pair).  init_const =
+        (n, 2) float32 host array of (dx, dy) per pair: tvl1_calc_batch_const_init.  auto_shift
+        = R: tvl1_calc_batch_auto_init with max_shift R; returns (stats dicts, shift dicts).
+        At most one of init, init_const and auto_shift."""
+        if sum(x is not None for x in (init, init_const, auto_shift)) > 1:
+            raise ValueError("init, init_const and auto_shift exclude one another")
+        if init_const is not None:
+            init_const = np.ascontiguousarray(init_const, np.float32)
+            if init_const.shape != (n, 2):
+                raise ValueError(f"init_const must have shape ({n}, 2), got {init_const.shape}")
         sts = (TVL1Stats * n)()
         wis = []
         if warp_iters:
@@ -426,7 +450,22 @@ class Engine:
                 sts[b].warp_iterations = wi.ctypes.data_as(C.POINTER(C.c_int32))
                 sts[b].warp_iterations_capacity = cap
                 wis.append(wi)
-        if init is None:
+        shifts = None
+        if init_const is not None:
+            rc = self.lib.tvl1_calc_batch_const_init(
+                self.ctx, n, C.c_void_p(dI0), pitch0, stride0, C.c_void_p(dI1), pitch1, stride1, w,
+                h, init_const.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(du), C.c_void_p(dv),
+                flow_pitch, flow_stride, sts, C.c_void_p(stream) if stream else None)
+            self._check(rc, "tvl1_calc_batch_const_init")
+        elif auto_shift is not None:
+            rs = (TVL1Shift * max(1, n))()
+            rc = self.lib.tvl1_calc_batch_auto_init(
+                self.ctx, n, C.c_void_p(dI0 or None), pitch0, stride0, C.c_void_p(dI1 or None),
+                pitch1, stride1, w, h, int(auto_shift), rs, C.c_void_p(du), C.c_void_p(dv),
+                flow_pitch, flow_stride, sts, C.c_void_p(stream) if stream else None)
+            self._check(rc, "tvl1_calc_batch_auto_init")
+            shifts = [shift_dict(rs[b]) for b in range(n)]
+        elif init is None:
             rc = self.lib.tvl1_calc_batch(self.ctx, n, C.c_void_p(dI0), pitch0, stride0,
                                           C.c_void_p(dI1), pitch1, stride1, w, h, C.c_void_p(du),
                                           C.c_void_p(dv), flow_pitch, flow_stride, sts,
@@ -447,7 +486,7 @@ class Engine:
             for b in range(n):
                 L = out[b]["levels"]
                 out[b]["warp_iters"] = wis[b][: L * self.params.warps].reshape(L, self.params.warps)
-        return out
+        return out if shifts is None else (out, shifts)
 
     def find_alignment(self, d1: int, pitch1: int, w1: int, h1: int, d0: int, pitch0: int,
                        w0: int, h0: int, **kw):

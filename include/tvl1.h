@@ -365,6 +365,38 @@ tvl1_status tvl1_estimate_shift_batch(tvl1_ctx *ctx, int32_t n, const uint8_t *I
                                       size_t pair_stride1, int32_t w, int32_t h,
                                       int32_t max_shift, tvl1_shift *out, void *stream);
 
+/* ---- Batched solves seeded by one constant per pair (added under ABI 9) ----
+ * tvl1_calc_batch whose pair b starts from the flow (dx_b, dy_b) everywhere: its flow and
+ * per-warp iteration counts are those of tvl1_calc_init from two planes filled with (dx_b,
+ * dy_b) (bit-identical, as tvl1_calc_batch_init's), but no such plane is stored or read: the
+ * first step of the seed's pyramid is evaluated from the constant, per px (its bilinear
+ * weights are rounded, so a level of that pyramid is not one value).  seed_xy: HOST, 2 n
+ * floats (dx_0, dy_0, dx_1, ...), copied before the call returns.  NULL seed_xy, a value that
+ * is not finite, or a ctx with profile = 1 is TVL1_EINVAL before anything is launched.
+ * gamma != 0 solves the pairs one by one through tvl1_calc_init's path (the constant is
+ * then written out as planes in scratch of one pair's size). */
+tvl1_status tvl1_calc_batch_const_init(tvl1_ctx *ctx, int32_t n,
+                                       const uint8_t *I0, size_t pitch0, size_t pair_stride0,
+                                       const uint8_t *I1, size_t pitch1, size_t pair_stride1,
+                                       int32_t width, int32_t height, const float *seed_xy,
+                                       float *u, float *v, size_t flow_pitch,
+                                       size_t flow_pair_stride, tvl1_stats *stats, void *stream);
+
+/* tvl1_estimate_shift_batch and tvl1_calc_batch_const_init in one call, the seeds handed over
+ * on the device: shifts[b] (HOST, n records) is tvl1_estimate_shift of pair b, and pair b's
+ * flow is tvl1_calc_batch_const_init's with ((float)dx_b, (float)dy_b).  The argument checks
+ * of tvl1_estimate_shift_batch apply first and unchanged (max_shift, 4 max_shift <= min(w, h),
+ * w h <= 2^26), then tvl1_calc_batch's; nothing is launched after an error.  The estimate is
+ * enqueued ahead of the solve with no host wait between them; the records are on the host
+ * when the call returns (it synchronizes the stream once the solve is enqueued). */
+tvl1_status tvl1_calc_batch_auto_init(tvl1_ctx *ctx, int32_t n,
+                                      const uint8_t *I0, size_t pitch0, size_t pair_stride0,
+                                      const uint8_t *I1, size_t pitch1, size_t pair_stride1,
+                                      int32_t width, int32_t height, int32_t max_shift,
+                                      tvl1_shift *shifts,
+                                      float *u, float *v, size_t flow_pitch,
+                                      size_t flow_pair_stride, tvl1_stats *stats, void *stream);
+
 /* The estimate's cost kernel as a call of its own: sad[(dy + r) (2r + 1) + (dx + r)] =
  * S(cx + dx, cy + dy) for dx, dy in [-r, r], r = radius in 1 .. 4 (else TVL1_EINVAL), on one
  * level (no pyramid).  A shift whose overlap is empty reports 0.  sad: (2r + 1)^2 HOST values;
