@@ -2,7 +2,9 @@
  * tests/test_host_hardening_cpu.py::test_oracle_under_asan).  Solves small synthetic pairs
  * at odd sizes through every code path of the restatement: both profiles, gamma, median,
  * fixed work, a pyramid that bottoms out, 1x1 / 16x16 edge sizes, and the seeded entry in
- * both arithmetics (a pitched seed whose taps leave the frame on every side); and the
+ * both arithmetics (a pitched seed whose taps leave the frame on every side); the fast branch
+ * (orc_set_approx_prims with C stand-ins: 1.0f / x and sqrtf) at every size, 1x1 included,
+ * unseeded, seeded and from f32 frames, with a failing primitive, and uninstalled again; and the
  * pre-alignment restatement (tvl1_oracle_align.c) at its edges: frames with one candidate
  * px and with none, a pitched view, a level quota sum above nfeatures, train sets of 0, 1
  * and 65 descriptors, singular and far-off warps, and a pair of different sizes. */
@@ -11,7 +13,23 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <math.h>
+
 #include "tvl1_oracle.h"
+
+/* stand-ins for the fast branch's primitives; g_prim_calls counts them, g_prim_fail makes the
+ * call of that number fail */
+static int g_prim_calls = 0, g_prim_fail = -1;
+static int rcp_c(const float *in, float *out, size_t n) {
+  if (g_prim_calls++ == g_prim_fail) return 1;
+  for (size_t i = 0; i < n; ++i) out[i] = 1.0f / in[i];
+  return 0;
+}
+static int sqrt_c(const float *in, float *out, size_t n) {
+  if (g_prim_calls++ == g_prim_fail) return 1;
+  for (size_t i = 0; i < n; ++i) out[i] = sqrtf(in[i]);
+  return 0;
+}
 
 static void pair(int w, int h, unsigned seed, uint8_t *a, uint8_t *b) {
   for (int y = 0; y < h; ++y)
@@ -197,6 +215,50 @@ int main(void) {
         fprintf(stderr, "%dx%d seeded fast_math %d: status %d, profile 1: %d\n", w, h, fm, rc, rc1);
         ++fails;
       }
+    }
+    /* the fast branch: unseeded (stopping rule, median, fixed work), seeded, f32 frames; a
+     * primitive that fails on its 1st .. 4th call; then uninstalled (IEEE, no call) */
+    {
+      float *fa = malloc(sizeof(float) * w * h), *fb = malloc(sizeof(float) * w * h);
+      for (int i = 0; i < w * h; ++i) fa[i] = (float)a[i] / 255.0f, fb[i] = (float)b[i] / 255.0f;
+      orc_set_approx_prims(rcp_c, sqrt_c);
+      for (int variant = 0; variant < 9; ++variant) {
+        tvl1_params p = {0.25, 0.05, 0.3, 10, 3, 0.01, 300, 0.8, 0.0, 0, 1, 1, 0, 30, 10};
+        if (variant == 1) p.median_filtering = 3;
+        if (variant == 2) p.epsilon = 0.0, p.iterations = 3;
+        g_prim_calls = 0;
+        g_prim_fail = variant >= 5 ? variant - 5 : -1;
+        tvl1_stats st;
+        memset(&st, 0, sizeof st);
+        int rc;
+        if (variant == 3)
+          rc = orc_tvl1_calc_init(&p, a, (size_t)w, b, (size_t)w, w, h, u0, v0, sizeof(float) * sp,
+                                  u, v, sizeof(float) * (size_t)w, &st);
+        else if (variant == 4)
+          rc = orc_tvl1_calc_f32(&p, fa, sizeof(float) * (size_t)w, fb, sizeof(float) * (size_t)w,
+                                 w, h, u, v, sizeof(float) * (size_t)w, &st);
+        else
+          rc = orc_tvl1_calc(&p, a, (size_t)w, b, (size_t)w, w, h, u, v,
+                             sizeof(float) * (size_t)w, &st);
+        const int want = variant >= 5 ? TVL1_EHIP : TVL1_OK;
+        if (rc != want || g_prim_calls == 0 ||
+            (rc == TVL1_OK && g_prim_calls != 2 * (int)st.iterations_total + 2 * p.warps * st.levels)) {
+          fprintf(stderr, "%dx%d fast variant %d: status %d, %d primitive calls\n", w, h, variant,
+                  rc, g_prim_calls);
+          ++fails;
+        }
+      }
+      orc_set_approx_prims(NULL, NULL);
+      g_prim_calls = 0, g_prim_fail = -1;
+      tvl1_params p = {0.25, 0.05, 0.3, 10, 3, 0.01, 300, 0.8, 0.0, 0, 1, 1, 0, 30, 10};
+      const int rc = orc_tvl1_calc(&p, a, (size_t)w, b, (size_t)w, w, h, u, v,
+                                   sizeof(float) * (size_t)w, NULL);
+      if (rc != 0 || g_prim_calls != 0) {
+        fprintf(stderr, "%dx%d fast uninstalled: status %d, %d primitive calls\n", w, h, rc, g_prim_calls);
+        ++fails;
+      }
+      free(fa);
+      free(fb);
     }
     free(u0);
     free(v0);

@@ -13,6 +13,46 @@ from optflow_amd.capi import (STATUS, TVL1_MAX_LEVELS, TVL1Error, TVL1Params, TV
                               _f32_ptr, _u8_ptr, make_params, stats_dict)
 
 ORACLE_SO = Path(__file__).resolve().parent / "liboracle_tvl1.so"
+FASTPRIMS_SO = Path(__file__).resolve().parent / "libtvl1_fastprims.so"
+
+# orc_vec_fn (tvl1_oracle.h): out[i] = f(in[i]) for i < n, non-zero on failure
+VEC_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t)
+_fastprims = None
+
+
+def device_prims():
+    """(rcp, sqrt): the device's v_rcp_f32 / v_sqrt_f32 as orc_vec_fn functions of
+    libtvl1_fastprims.so (oracle/fast_prims.hip; needs a GPU to be called)."""
+    global _fastprims
+    if _fastprims is None:
+        if not FASTPRIMS_SO.exists():
+            raise FileNotFoundError(f"{FASTPRIMS_SO} not built (run __graft_entry__.build())")
+        _fastprims = C.CDLL(str(FASTPRIMS_SO))
+        for f in (_fastprims.fastprims_rcp, _fastprims.fastprims_sqrt):
+            f.restype = C.c_int
+            f.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]
+    return _fastprims.fastprims_rcp, _fastprims.fastprims_sqrt
+
+
+def prim_apply(fn, x: np.ndarray) -> np.ndarray:
+    """One orc_vec_fn primitive on a float32 array (the tests' self-check of the device's)."""
+    a = np.ascontiguousarray(x, np.float32).ravel()
+    out = np.empty_like(a)
+    if fn(_f32_ptr(a), _f32_ptr(out), a.size) != 0:
+        raise TVL1Error("oracle: an approx primitive failed")
+    return out.reshape(np.shape(x))
+
+
+def _install_prims(lib, approx):
+    """orc_set_approx_prims for oracle_calc's approx=; returns what must stay alive."""
+    if approx is None:
+        return None
+    rcp, sqrt = device_prims() if isinstance(approx, str) and approx == "device" else approx
+    lib.orc_set_approx_prims.restype = None
+    lib.orc_set_approx_prims.argtypes = [C.c_void_p, C.c_void_p]
+    # the addresses go from one library to the other: no Python frame sits in a device call
+    lib.orc_set_approx_prims(C.cast(rcp, C.c_void_p), C.cast(sqrt, C.c_void_p))
+    return rcp, sqrt
 
 
 def load_oracle(so: str | Path | None = None) -> C.CDLL:
@@ -45,11 +85,24 @@ def load_oracle(so: str | Path | None = None) -> C.CDLL:
 
 def oracle_calc(I0: np.ndarray, I1: np.ndarray, params: TVL1Params | None = None,
                 warp_iters: bool = True, threads: int | None = None,
-                so: str | Path | None = None, init=None):
+                so: str | Path | None = None, init=None, approx=None):
     """Run the CPU restatement on host u8 images (or float32 images: tvl1_calc_f32's
     contract, values scaled by 255); returns (u, v, stats, warp_iters).  init = (u0, v0):
-    the solve of tvl1_calc_init from that float32 seed (u8 frames, profile 0)."""
+    the solve of tvl1_calc_init from that float32 seed (u8 frames, profile 0).
+    approx: the primitives of the oracle's fast branch (fast_math = 1; orc_set_approx_prims) --
+    None: none, fast_math = 1 is solved in IEEE; "device": the GPU's own v_rcp_f32 /
+    v_sqrt_f32 (device_prims); or a pair (rcp, sqrt) of ctypes callables of VEC_FN's shape.
+    They are uninstalled when the solve returns."""
     lib = load_oracle(so)
+    keep = _install_prims(lib, approx)
+    try:
+        return _oracle_calc(lib, I0, I1, params, warp_iters, threads, init)
+    finally:
+        if keep is not None:
+            lib.orc_set_approx_prims(None, None)
+
+
+def _oracle_calc(lib, I0, I1, params, warp_iters, threads, init):
     if threads:
         lib.orc_set_num_threads(int(threads))
     params = params or make_params()
@@ -182,16 +235,16 @@ def oracle_postprocess_affine(u: np.ndarray, v: np.ndarray, I1: np.ndarray, flow
 # ---- stopping-rule robustness: the oracle's per-check
 # error / scaledEps trace and an alternative residual accumulation order
 def oracle_check_trace(I0: np.ndarray, I1: np.ndarray, params: TVL1Params | None = None,
-                       residual_mode: int = 0, cap: int = 1 << 16, init=None):
+                       residual_mode: int = 0, cap: int = 1 << 16, init=None, approx=None):
     """oracle_calc with every check recorded: returns (u, v, stats, warp_iters, trace) where
     trace is an (n, 4) array of (level, warp, n, error / scaledEps).  residual_mode 1 sums the
-    residual in float, rows reversed (orc_set_residual_mode).  init: oracle_calc's seed."""
+    residual in float, rows reversed (orc_set_residual_mode).  init, approx: oracle_calc's seed and fast-branch primitives."""
     lib = load_oracle()
     buf = np.zeros((cap, 4), np.float64)
     lib.orc_set_residual_mode(int(residual_mode))
     lib.orc_set_check_trace(buf.ctypes.data_as(C.c_void_p), cap)
     try:
-        u, v, st, wi = oracle_calc(I0, I1, params, init=init)
+        u, v, st, wi = oracle_calc(I0, I1, params, init=init, approx=approx)
         n = int(lib.orc_check_trace_count())
     finally:
         lib.orc_set_check_trace(None, 0)

@@ -28,8 +28,15 @@
  * measured.  The rule, NVPTX's DAG combine with aggressive FMA fusion: an
  * add or subtract with a multiply operand becomes one fma, the LEFT operand's product when
  * both are products (a*b + c*d -> fma(a, b, c*d)); a - b*c -> fma(-b, c, a).  Each site is
- * marked FMA below.  fast_math = 1 (approximate division / sqrt) has no exact C form: the
- * oracle solves it in IEEE and the engine is held to the tolerance bar.
+ * marked FMA below.
+ *
+ * fast mode (tvl1_params.fast_math = 1, the reference build's CUDA_FAST_MATH): fma mode's
+ * operation sequence with four expressions changed, each marked FAST below -- warpBackward's
+ * coeff = rcp(wsum), the TH step's fi = -rho * rcp(grad), the projection's g = sqrt(..) and
+ * p' = fma(taut, du, p) * rcp(ng).  rcp and sqrt are the device's approximate instructions,
+ * pure functions of one float with no C form, so they are supplied from outside
+ * (orc_set_approx_prims) and called on whole planes.  With none installed fast_math = 1 is
+ * solved in IEEE.
  */
 #include "tvl1_oracle.h"
 
@@ -166,6 +173,15 @@ void orc_centered_gradient(const float *I, int w, int h, float *Ix, float *Iy) {
     }
 }
 
+/* fast mode's two primitives (see the header comment); both or neither.  Process-global, not
+ * thread-safe: test infrastructure. */
+static orc_vec_fn g_rcp = NULL, g_sqrt = NULL;
+
+void orc_set_approx_prims(orc_vec_fn rcp, orc_vec_fn sqrt_fn) {
+  g_rcp = rcp && sqrt_fn ? rcp : NULL;
+  g_sqrt = rcp && sqrt_fn ? sqrt_fn : NULL;
+}
+
 /* [A.3] Keys cubic kernel, a = -0.5 (tvl1flow.cu `cubic`). */
 static inline float cubic(float x, int fma_mode) {
   x = fabsf(x);
@@ -182,6 +198,59 @@ static inline float cubic(float x, int fma_mode) {
 /* [A.3] warpBackward: 4x4(5x5) cubic gather of I1, I1x, I1y at (x+u1, y+u2) with
  * texture clamp, weight-normalised; grad = I1wx^2 + I1wy^2;
  * rho_c = I1w - I1wx*u1 - I1wy*u2 - I0. */
+/* the gather of one px: sum, sumx, sumy, wsum in out[0..3] */
+static inline void warp_gather_px(const float *I1, const float *I1x, const float *I1y, float u1v,
+                                  float u2v, int x, int y, int w, int h, int fma_mode,
+                                  float out[4]) {
+  const float wx = (float)x + u1v;
+  const float wy = (float)y + u2v;
+  const int xmin = (int)ceilf(wx - 2.0f);
+  const int xmax = (int)floorf(wx + 2.0f);
+  const int ymin = (int)ceilf(wy - 2.0f);
+  const int ymax = (int)floorf(wy + 2.0f);
+  float sum = 0.0f, sumx = 0.0f, sumy = 0.0f, wsum = 0.0f;
+  for (int cy = ymin; cy <= ymax; ++cy) {
+    const int ry = imin(imax(cy, 0), h - 1);
+    for (int cx = xmin; cx <= xmax; ++cx) {
+      const int rx = imin(imax(cx, 0), w - 1);
+      const float wgt = cubic(wx - (float)cx, fma_mode) * cubic(wy - (float)cy, fma_mode);
+      const size_t j = IDX(rx, ry, w);
+      if (fma_mode) { /* FMA: sum + w*I -> fma(w, I, sum) */
+        sum = fmaf(wgt, I1[j], sum);
+        sumx = fmaf(wgt, I1x[j], sumx);
+        sumy = fmaf(wgt, I1y[j], sumy);
+      } else {
+        sum = sum + wgt * I1[j];
+        sumx = sumx + wgt * I1x[j];
+        sumy = sumy + wgt * I1y[j];
+      }
+      wsum = wsum + wgt;
+    }
+  }
+  out[0] = sum, out[1] = sumx, out[2] = sumy, out[3] = wsum;
+}
+
+/* normalisation by coeff (1 / wsum, or FAST: rcp(wsum)), grad and rho_c of one px */
+static inline void warp_finish_px(float sum, float sumx, float sumy, float coeff, float u1v,
+                                  float u2v, float I0v, int fma_mode, float *I1wx, float *I1wy,
+                                  float *grad, float *rho_c) {
+  const float I1wv = sum * coeff;
+  const float I1wxv = sumx * coeff;
+  const float I1wyv = sumy * coeff;
+  *I1wx = I1wxv;
+  *I1wy = I1wyv;
+  const float Ix2 = I1wxv * I1wxv;
+  const float Iy2 = I1wyv * I1wyv;
+  if (fma_mode) { /* FMA: Ix2 + Iy2 -> fma(I1wx, I1wx, Iy2); the two products of rho_c
+                   * fused into the running difference */
+    *grad = fmaf(I1wxv, I1wxv, Iy2);
+    *rho_c = fmaf(-I1wyv, u2v, fmaf(-I1wxv, u1v, I1wv)) - I0v;
+  } else {
+    *grad = Ix2 + Iy2;
+    *rho_c = I1wv - I1wxv * u1v - I1wyv * u2v - I0v;
+  }
+}
+
 static void warp_backward(const float *I0, const float *I1, const float *I1x, const float *I1y,
                           const float *u1, const float *u2, int w, int h, float *I1wx,
                           float *I1wy, float *grad, float *rho_c, int fma_mode) {
@@ -189,50 +258,45 @@ static void warp_backward(const float *I0, const float *I1, const float *I1x, co
   for (int y = 0; y < h; ++y)
     for (int x = 0; x < w; ++x) {
       const size_t i = IDX(x, y, w);
-      const float u1v = u1[i];
-      const float u2v = u2[i];
-      const float wx = (float)x + u1v;
-      const float wy = (float)y + u2v;
-      const int xmin = (int)ceilf(wx - 2.0f);
-      const int xmax = (int)floorf(wx + 2.0f);
-      const int ymin = (int)ceilf(wy - 2.0f);
-      const int ymax = (int)floorf(wy + 2.0f);
-      float sum = 0.0f, sumx = 0.0f, sumy = 0.0f, wsum = 0.0f;
-      for (int cy = ymin; cy <= ymax; ++cy) {
-        const int ry = imin(imax(cy, 0), h - 1);
-        for (int cx = xmin; cx <= xmax; ++cx) {
-          const int rx = imin(imax(cx, 0), w - 1);
-          const float wgt = cubic(wx - (float)cx, fma_mode) * cubic(wy - (float)cy, fma_mode);
-          const size_t j = IDX(rx, ry, w);
-          if (fma_mode) { /* FMA: sum + w*I -> fma(w, I, sum) */
-            sum = fmaf(wgt, I1[j], sum);
-            sumx = fmaf(wgt, I1x[j], sumx);
-            sumy = fmaf(wgt, I1y[j], sumy);
-          } else {
-            sum = sum + wgt * I1[j];
-            sumx = sumx + wgt * I1x[j];
-            sumy = sumy + wgt * I1y[j];
-          }
-          wsum = wsum + wgt;
-        }
-      }
-      const float coeff = 1.0f / wsum;
-      const float I1wv = sum * coeff;
-      const float I1wxv = sumx * coeff;
-      const float I1wyv = sumy * coeff;
-      I1wx[i] = I1wxv;
-      I1wy[i] = I1wyv;
-      const float Ix2 = I1wxv * I1wxv;
-      const float Iy2 = I1wyv * I1wyv;
-      if (fma_mode) { /* FMA: Ix2 + Iy2 -> fma(I1wx, I1wx, Iy2); the two products of rho_c
-                       * fused into the running difference */
-        grad[i] = fmaf(I1wxv, I1wxv, Iy2);
-        rho_c[i] = fmaf(-I1wyv, u2v, fmaf(-I1wxv, u1v, I1wv)) - I0[i];
-      } else {
-        grad[i] = Ix2 + Iy2;
-        rho_c[i] = I1wv - I1wxv * u1v - I1wyv * u2v - I0[i];
-      }
+      float g[4];
+      warp_gather_px(I1, I1x, I1y, u1[i], u2[i], x, y, w, h, fma_mode, g);
+      const float coeff = 1.0f / g[3];
+      warp_finish_px(g[0], g[1], g[2], coeff, u1[i], u2[i], I0[i], fma_mode, I1wx + i, I1wy + i,
+                     grad + i, rho_c + i);
     }
+}
+
+/* fast mode's scratch planes: s0..s2 of w*h floats, a and b of 2*w*h */
+typedef struct {
+  float *s0, *s1, *s2, *a, *b;
+} fast_bufs;
+
+/* FAST warpBackward as array passes, each primitive called on a whole plane outside any
+ * OpenMP region: gather, coeff = rcp(wsum), finish in fma mode's expressions; then
+ * rgrad = rcp(grad), once per warp (grad is a warp constant).  Non-zero: a primitive failed. */
+static int warp_backward_fast(const float *I0, const float *I1, const float *I1x,
+                              const float *I1y, const float *u1, const float *u2, int w, int h,
+                              float *I1wx, float *I1wy, float *grad, float *rho_c, float *rgrad,
+                              const fast_bufs *fb) {
+  const size_t N = (size_t)w * h;
+  float *sum = fb->s0, *sumx = fb->s1, *sumy = fb->s2, *wsum = fb->a, *coeff = fb->b;
+#pragma omp parallel for schedule(static)
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) {
+      const size_t i = IDX(x, y, w);
+      float g[4];
+      warp_gather_px(I1, I1x, I1y, u1[i], u2[i], x, y, w, h, 1, g);
+      sum[i] = g[0], sumx[i] = g[1], sumy[i] = g[2], wsum[i] = g[3];
+    }
+  if (g_rcp(wsum, coeff, N)) return 1;
+#pragma omp parallel for schedule(static)
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) {
+      const size_t i = IDX(x, y, w);
+      warp_finish_px(sum[i], sumx[i], sumy[i], coeff[i], u1[i], u2[i], I0[i], 1, I1wx + i,
+                     I1wy + i, grad + i, rho_c + i);
+    }
+  return g_rcp(grad, rgrad, N) != 0;
 }
 
 void orc_warp_backward(const float *I0, const float *I1, const float *I1x, const float *I1y,
@@ -287,12 +351,14 @@ static void trace_check(int level, int warp, int n, double ratio) {
   if (g_trace) ++g_trace_n;
 }
 
-/* [A.3] estimateU: TH thresholding + u = v + theta * div(p). */
+/* [A.3] estimateU: TH thresholding + u = v + theta * div(p).  rgrad (fast mode, else NULL):
+ * rcp(grad) per px. */
 static double estimate_u(const float *I1wx, const float *I1wy, const float *grad,
                          const float *rho_c, const float *p11, const float *p12,
                          const float *p21, const float *p22, const float *p31,
                          const float *p32, float *u1, float *u2, float *u3, int w, int h,
-                         float l_t, float theta, float gamma, int calc_error, int fma_mode) {
+                         float l_t, float theta, float gamma, int calc_error, int fma_mode,
+                         const float *rgrad) {
   double *rows = calc_error ? (double *)calloc((size_t)h, sizeof(double)) : NULL;
   const int fmode = calc_error && g_resid_mode == 1;
   float *frows = fmode ? (float *)calloc((size_t)h, sizeof(float)) : NULL;
@@ -305,6 +371,9 @@ static double estimate_u(const float *I1wx, const float *I1wy, const float *grad
       const float I1wxv = I1wx[i];
       const float I1wyv = I1wy[i];
       const float gradv = grad[i];
+      /* FAST: fi = -rho * rcp(grad), formed for every px (grad = 0 gives -rho * inf, possibly
+       * NaN) and consumed only where grad > FLT_EPSILON */
+      const float rg = rgrad ? rgrad[i] : 0.0f;
       const float u1o = u1[i];
       const float u2o = u2[i];
       const float u3o = gamma != 0.0f ? u3[i] : 0.0f;
@@ -314,6 +383,7 @@ static double estimate_u(const float *I1wx, const float *I1wy, const float *grad
        * still turns a -0 sum into +0) */
       const float rho = fma_mode ? rho_c[i] + fmaf(gamma, u3o, fmaf(I1wxv, u1o, I1wyv * u2o))
                                  : rho_c[i] + (I1wxv * u1o + I1wyv * u2o + gamma * u3o);
+      const float fi_fast = -rho * rg;
       float d1 = 0.0f, d2 = 0.0f, d3 = 0.0f;
       if (rho < -l_t * gradv) {
         d1 = l_t * I1wxv;
@@ -324,7 +394,7 @@ static double estimate_u(const float *I1wx, const float *I1wy, const float *grad
         d2 = -l_t * I1wyv;
         if (gamma != 0.0f) d3 = -l_t * gamma;
       } else if (gradv > FLT_EPSILON) {
-        const float fi = -rho / gradv;
+        const float fi = rgrad ? fi_fast : -rho / gradv;
         d1 = fi * I1wxv;
         d2 = fi * I1wyv;
         if (gamma != 0.0f) d3 = fi * gamma;
@@ -372,7 +442,7 @@ double orc_estimate_u(const float *I1wx, const float *I1wy, const float *grad,
                       const float *p32, float *u1, float *u2, float *u3, int w, int h,
                       float l_t, float theta, float gamma, int calc_error) {
   return estimate_u(I1wx, I1wy, grad, rho_c, p11, p12, p21, p22, p31, p32, u1, u2, u3, w, h,
-                    l_t, theta, gamma, calc_error, 0);
+                    l_t, theta, gamma, calc_error, 0, NULL);
 }
 
 /* hypotf restated as sqrt(a*a + b*b) (FMA: fma(a, a, b*b)); CUDA's library hypotf is not
@@ -425,6 +495,48 @@ void orc_estimate_dual(const float *u1, const float *u2, const float *u3, float 
                        float *p12, float *p21, float *p22, float *p31, float *p32, int w,
                        int h, float taut, float gamma) {
   estimate_dual(u1, u2, u3, p11, p12, p21, p22, p31, p32, w, h, taut, gamma, 0);
+}
+
+/* FAST estimateDualVariables (gamma = 0) as array passes: the squared norms of both
+ * components (fma mode's fma(ux, ux, uy*uy)), one sqrt call over the 2*w*h of them,
+ * ng = fma(taut, g, 1), one rcp call over both ng planes, then p' = fma(taut, du, p) * r --
+ * a product with the reciprocal, not a quotient.  Non-zero: a primitive failed. */
+static int estimate_dual_fast(const float *u1, const float *u2, float *p11, float *p12,
+                              float *p21, float *p22, int w, int h, float taut,
+                              const fast_bufs *fb) {
+  const size_t N = (size_t)w * h;
+  float *a = fb->a, *b = fb->b;
+#pragma omp parallel for schedule(static)
+  for (int y = 0; y < h; ++y) {
+    const int yn = imin(y + 1, h - 1);
+    for (int x = 0; x < w; ++x) {
+      const int xn = imin(x + 1, w - 1);
+      const size_t i = IDX(x, y, w);
+      const float u1x = u1[IDX(xn, y, w)] - u1[i], u1y = u1[IDX(x, yn, w)] - u1[i];
+      const float u2x = u2[IDX(xn, y, w)] - u2[i], u2y = u2[IDX(x, yn, w)] - u2[i];
+      a[i] = fmaf(u1x, u1x, u1y * u1y);
+      a[N + i] = fmaf(u2x, u2x, u2y * u2y);
+    }
+  }
+  if (g_sqrt(a, b, 2 * N)) return 1;
+#pragma omp parallel for schedule(static)
+  for (size_t i = 0; i < 2 * N; ++i) a[i] = fmaf(taut, b[i], 1.0f);
+  if (g_rcp(a, b, 2 * N)) return 1;
+#pragma omp parallel for schedule(static)
+  for (int y = 0; y < h; ++y) {
+    const int yn = imin(y + 1, h - 1);
+    for (int x = 0; x < w; ++x) {
+      const int xn = imin(x + 1, w - 1);
+      const size_t i = IDX(x, y, w);
+      const float u1x = u1[IDX(xn, y, w)] - u1[i], u1y = u1[IDX(x, yn, w)] - u1[i];
+      const float u2x = u2[IDX(xn, y, w)] - u2[i], u2y = u2[IDX(x, yn, w)] - u2[i];
+      p11[i] = fmaf(taut, u1x, p11[i]) * b[i];
+      p12[i] = fmaf(taut, u1y, p12[i]) * b[i];
+      p21[i] = fmaf(taut, u2x, p21[i]) * b[N + i];
+      p22[i] = fmaf(taut, u2y, p22[i]) * b[N + i];
+    }
+  }
+  return 0;
 }
 
 /* Build-only median filter: cv::medianBlur on CV_32F
@@ -526,7 +638,11 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
   /* fma mode for the gamma = 0 path with 0 <= tau/theta < inf (the engine's streaming
    * kernels; other parameter sets run IEEE there too) */
   const float taut_f = (float)(prm->tau / prm->theta);
-  const int fma_mode = prm->fast_math == 2 && !use_gamma && taut_f >= 0.0f && taut_f <= FLT_MAX;
+  const int contracting = !use_gamma && taut_f >= 0.0f && taut_f <= FLT_MAX;
+  /* fast mode: fma mode's sequence with the four FAST sites, when its primitives are installed */
+  const int fast_mode = prm->fast_math == 1 && contracting && g_rcp && g_sqrt;
+  const int fma_mode = (prm->fast_math == 2 && contracting) || fast_mode;
+  int rc = TVL1_OK;
 
   level_bufs lv[TVL1_MAX_LEVELS];
   memset(lv, 0, sizeof(lv));
@@ -552,6 +668,16 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
   float *p31 = use_gamma ? (float *)malloc(N0 * sizeof(float)) : NULL;
   float *p32 = use_gamma ? (float *)malloc(N0 * sizeof(float)) : NULL;
   float *tmp = prm->median_filtering > 1 ? (float *)malloc(N0 * sizeof(float)) : NULL;
+  fast_bufs fb = {NULL, NULL, NULL, NULL, NULL};
+  float *rgrad = NULL;
+  if (fast_mode) {
+    fb.s0 = (float *)malloc(N0 * sizeof(float));
+    fb.s1 = (float *)malloc(N0 * sizeof(float));
+    fb.s2 = (float *)malloc(N0 * sizeof(float));
+    fb.a = (float *)malloc(2 * N0 * sizeof(float));
+    fb.b = (float *)malloc(2 * N0 * sizeof(float));
+    rgrad = (float *)malloc(N0 * sizeof(float));
+  }
 
   int64_t level_iters[TVL1_MAX_LEVELS];
   memset(level_iters, 0, sizeof(level_iters));
@@ -614,8 +740,14 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
         orc_median(lv[s].u2, lw, lh, prm->median_filtering, tmp);
         memcpy(lv[s].u2, tmp, N * sizeof(float));
       }
-      warp_backward(lv[s].I0, lv[s].I1, I1x, I1y, lv[s].u1, lv[s].u2, lw, lh, I1wx, I1wy, grad,
-                    rho_c, fma_mode);
+      if (!fast_mode) {
+        warp_backward(lv[s].I0, lv[s].I1, I1x, I1y, lv[s].u1, lv[s].u2, lw, lh, I1wx, I1wy, grad,
+                      rho_c, fma_mode);
+      } else if (warp_backward_fast(lv[s].I0, lv[s].I1, I1x, I1y, lv[s].u1, lv[s].u2, lw, lh,
+                                    I1wx, I1wy, grad, rho_c, rgrad, &fb)) {
+        rc = TVL1_EHIP;
+        goto done;
+      }
       double error = DBL_MAX;
       double prevError = 0.0;
       int n;
@@ -623,7 +755,7 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
         const int calcError = (prm->epsilon > 0) && (n & 1) && (prevError < scaledEps);
         const double e = estimate_u(I1wx, I1wy, grad, rho_c, p11, p12, p21, p22, p31, p32,
                                     lv[s].u1, lv[s].u2, lv[s].u3, lw, lh, l_t, theta_f, gamma_f,
-                                    calcError, fma_mode);
+                                    calcError, fma_mode, fast_mode ? rgrad : NULL);
         if (calcError) {
           error = e;
           prevError = error;
@@ -633,8 +765,13 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
           error = DBL_MAX;
           prevError -= scaledEps;
         }
-        estimate_dual(lv[s].u1, lv[s].u2, lv[s].u3, p11, p12, p21, p22, p31, p32, lw, lh, taut,
-                      gamma_f, fma_mode);
+        if (!fast_mode) {
+          estimate_dual(lv[s].u1, lv[s].u2, lv[s].u3, p11, p12, p21, p22, p31, p32, lw, lh, taut,
+                        gamma_f, fma_mode);
+        } else if (estimate_dual_fast(lv[s].u1, lv[s].u2, p11, p12, p21, p22, lw, lh, taut, &fb)) {
+          rc = TVL1_EHIP;
+          goto done;
+        }
       }
       level_iters[s] += n;
       if (stats && stats->warp_iterations &&
@@ -677,6 +814,7 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
     stats->algorithmic_bytes = orc_survey_bytes(L, ws, hs, prm->warps, level_iters);
   }
 
+done:
   for (int s = 0; s < L; ++s) {
     free(lv[s].I0);
     free(lv[s].I1);
@@ -686,7 +824,8 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
   }
   free(I1x); free(I1y); free(I1wx); free(I1wy); free(grad); free(rho_c);
   free(p11); free(p12); free(p21); free(p22); free(p31); free(p32); free(tmp);
-  return TVL1_OK;
+  free(fb.s0); free(fb.s1); free(fb.s2); free(fb.a); free(fb.b); free(rgrad);
+  return rc;
 }
 
 int orc_tvl1_calc(const tvl1_params *prm, const uint8_t *I0, size_t pitch0,

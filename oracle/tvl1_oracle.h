@@ -92,12 +92,24 @@ int orc_tvl1_calc_f32(const tvl1_params *params, const float *I0, size_t pitch0,
                       size_t flow_pitch, tvl1_stats *stats);
 
 /* ... and tvl1_calc_host_init's: the solve from the seed (u0, v0), row pitch init_pitch bytes
- * (SURVEY A.2b), in IEEE or, with fast_math = 2, in the contracted arithmetic; TVL1_EINVAL for
+ * (SURVEY A.2b), in IEEE, fma (fast_math = 2) or fast arithmetic (below); TVL1_EINVAL for
  * a null seed, a bad init_pitch or profile = 1 */
 int orc_tvl1_calc_init(const tvl1_params *params, const uint8_t *I0, size_t pitch0,
                        const uint8_t *I1, size_t pitch1, int w, int h, const float *u0,
                        const float *v0, size_t init_pitch, float *u, float *v,
                        size_t flow_pitch, tvl1_stats *stats);
+
+/* fast mode (fast_math = 1): fma mode's operation sequence with the device's approximate
+ * reciprocal and square root at the four sites tvl1_oracle.c marks FAST.  The two are pure
+ * functions of one float with no C form, so the caller supplies them: out[i] = f(in[i]) for
+ * i < n (in and out do not overlap), non-zero on failure, which the solve returns as
+ * TVL1_EHIP.  They are called on whole planes, outside any OpenMP region.  The fast branch
+ * runs in orc_tvl1_calc, orc_tvl1_calc_f32 and orc_tvl1_calc_init when both are installed,
+ * fast_math == 1 and fma mode's own conditions hold (profile 0, gamma == 0, 0 <= tau/theta <=
+ * FLT_MAX); with nothing installed (either NULL uninstalls both) fast_math = 1 is solved in
+ * IEEE.  Process-global, not thread-safe. */
+typedef int (*orc_vec_fn)(const float *in, float *out, size_t n);
+void orc_set_approx_prims(orc_vec_fn rcp, orc_vec_fn sqrt_fn);
 
 /* solve_wrapper post-ops (optflow.cpp:445-473) on host buffers */
 void orc_postprocess(float *u, float *v, size_t flow_pitch, const uint8_t *I1, size_t pitch1,

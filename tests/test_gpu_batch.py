@@ -114,16 +114,31 @@ def test_batch_coarsest_level_on_chip_edges(built, w, h, kw, math):
     check_against_oracle(p, I0s, I1s, u, v, st)
 
 
+# The 260-pair batch and the pairs of it that are compared.  Seed 12: at the earlier seed 7 a
+# check of pair 63 sat 5.9e-5 (IEEE), 6.1e-5 (fma, fast) from a threshold, under the 1e-4 a
+# stopping decision needs to be comparable (tests/test_residual_margin_cpu.py); at 12 the
+# selected pairs clear it by 8.7e-4 in all three arithmetics
+# (tests/test_oracle_fast_cpu.py::test_two_chunk_batch_margins, tests/test_gpu_fast_bitwise.py).
+TWO_CHUNKS = dict(n=260, w=64, h=24, seed=12, identical=5, kw=dict(nscales=3, warps=2),
+                  sel=[0, 5, 63, 64, 200, 255, 256, 259])
+
+
+def two_chunk_pairs():
+    c = TWO_CHUNKS
+    I0s, I1s = pairs(c["n"], c["w"], c["h"], seed=c["seed"])
+    I1s[c["identical"]] = I0s[c["identical"]]
+    return I0s, I1s
+
+
 def test_batch_larger_than_one_chunk(built):
     """260 pairs: two chunks (256 + 4), plus an identical pair (stops at n = 2 everywhere)."""
-    p = capi.make_params(nscales=3, warps=2)
+    p = capi.make_params(**TWO_CHUNKS["kw"])
     eng = capi.Engine(p)
-    I0s, I1s = pairs(260, 64, 24, seed=7)
-    I1s[5] = I0s[5]
+    I0s, I1s = two_chunk_pairs()
     u, v, st = run_batch(eng, I0s, I1s)
     eng.close()
     assert np.all(u[5] == 0) and np.all(st[5]["warp_iters"] == 2)
-    sel = [0, 5, 63, 64, 200, 255, 256, 259]
+    sel = TWO_CHUNKS["sel"]
     check_against_oracle(p, I0s[sel], I1s[sel], u[sel], v[sel], [st[b] for b in sel])
 
 

@@ -22,8 +22,8 @@ kb_iterate_roll<K,1> (default), kb_iterate_roll<K,2> (TVL1_BATCH_PX1_W=0), kb_wa
 (TVL1_BATCH_FUSE=0; fixed work always), segments of 8 rows (TVL1_BATCH_SEG_MIN=8).
 
 Per case: the oracle's levels and sizes, its per-warp iteration counts, and its u and v bit for
-bit (on its finite mask where tau < 0).  fast_math = 1 has no bitwise reference and profile 1
-its own tests: neither is here.
+bit (on its finite mask where tau < 0).  fast_math = 1 runs this table bitwise against the
+oracle's fast branch in tests/test_gpu_fast_bitwise.py; profile 1 has its own tests.
 """
 import re
 

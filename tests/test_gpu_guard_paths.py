@@ -12,9 +12,10 @@ Inputs that send whole wavefronts, and single lanes of a wavefront, through the 
 on every iteration kernel the knobs reach (the blocked k_iterate_tb4 for the long passes, the
 streaming k_iterate_roll<3|4, 2> and the mid-check pass, both forms of k_warp_iter) and in the
 three arithmetic modes.  IEEE and fma mode: bitwise against the oracle, with equal per-warp
-iteration counts.  The approximate mode has no oracle restatement and no guarded forms (v_rcp /
-v_sqrt on every lane); it is held to tests/test_gpu_fastmath.py's bar against the IEEE oracle
-(the oracle's iteration schedule, EPE budget) on these inputs.
+iteration counts.  The approximate mode has no guarded forms (v_rcp / v_sqrt on every lane); it
+is bitwise the oracle's fast branch on these inputs in tests/test_gpu_fast_bitwise.py, and held
+here to tests/test_gpu_fastmath.py's bar against the IEEE oracle (the oracle's iteration
+schedule, EPE budget).
 """
 import numpy as np
 import pytest

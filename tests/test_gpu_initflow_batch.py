@@ -116,9 +116,10 @@ def test_shared_seed_is_the_replicated_seed(built, name):
 @pytest.mark.parametrize("math", [0, 1, 2])
 @pytest.mark.parametrize("env", ["", "TVL1_BATCH_SMALL=0"])
 def test_seeded_batch_pair_is_the_single_seeded_solve(built, monkeypatch, math, env):
-    """Each pair of the batch must be tvl1_calc_init of that pair alone, bitwise.  fast_math 1
-    has no seeded reference: this equality is what holds its batched seed chain and on-chip
-    level.  IEEE and fma mode are also held to their references above."""
+    """Each pair of the batch must be tvl1_calc_init of that pair alone, bitwise.  This
+    equality is what holds fast_math 1's batched seed chain (its single seeded solves and its
+    on-chip level are bitwise the oracle's fast branch in tests/test_gpu_fast_bitwise.py).  IEEE
+    and fma mode are also held to their references above."""
     set_env(monkeypatch, env)
     case = ref.BATCH["strip6"]
     I0s, I1s, U0, V0 = batch_of(case)

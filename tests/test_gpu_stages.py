@@ -3,7 +3,8 @@
 TVL1_STAGES=2 sends every gamma = 0 pass of 2 or 4 iterations, on every level, to the kernel.
 Each solve is compared bitwise with the oracle -- u, v, per-warp iteration counts, number of
 checks -- and with the same solve under TVL1_STAGES=0 (k_iterate_roll / k_iterate_tb4), in
-IEEE and fma arithmetic; the approximate mode is held to tests/test_gpu_fastmath.py's budget.
+IEEE and fma arithmetic; the approximate mode is held to tests/test_gpu_fastmath.py's budget
+here and, bitwise against the oracle's fast branch, in tests/test_gpu_fast_bitwise.py.
 
 Shapes, the smallest at which the kernel can go wrong (K = 4: 120 output px per 128-px band,
 K = 2: 124; TVL1_ROLL_SEG=8 forces 8-row segments; a block runs rows + run-in + 2K - 1 steps in

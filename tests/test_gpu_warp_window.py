@@ -18,8 +18,9 @@ reaches the kernel, every parameter set and seed of the row through tvl1_calc_in
   kb_small_level          the default on-chip path, all five seeds as five pairs
 fast_math 0 and 2: the flow's bits and the per-warp counts are checker.oracle_calc(init=...)'s;
 single-pair fixed-work cases also count their iteration passes (kernel_launches[0]).
-fast_math 1 has no bitwise form: its fixed-work cases are held to tests/test_gpu_fastmath.py's
-bar against the IEEE reference, mean EPE <= 1e-3 px and at most 1e-3 of the px over 1e-2 px
+fast_math 1 is bitwise the oracle's fast branch on every row and parameter set in
+tests/test_gpu_fast_bitwise.py; here its fixed-work cases are also held to
+tests/test_gpu_fastmath.py's bar against the IEEE reference, mean EPE <= 1e-3 px and at most 1e-3 of the px over 1e-2 px
 (on the CPU the IEEE and fma references of these cases are at most 1.3e-5 px apart in the mean,
 no px over 1e-2: the bar is one the reference side meets).
 """
