@@ -42,7 +42,11 @@
 //     "auto" through tvl1_calc_batch_auto_init on the packed strips of each ROI key, with the
 //     per-pair path's range min(initialFlowMaxShift, 128, min(W, h) / 4), below 1 unseeded --
 //     with the same flows, outputs and stats_json entries; per-image seed keys still send a
-//     pair the per-pair way);
+//     pair the per-pair way); "consistency" (false, true or {"alpha", "beta"}: style 1 only; each
+//     ROI is also solved backward, the forward flow is scored against the backward one and
+//     zeroed where the forward-backward check fails), "consistencyOversample"
+//     (random_points candidates per point, default 4) and "consistencyOutput" (the score plane
+//     as {output}{suffix}_fb.tiff);
 //   * "style": 2 (from_list below): the average-flow alignment of a slice list that the
 //     reference declares and keeps disabled; keys "slices" | "file_list", "border",
 //     "save_flow" (DESIGN 11, and 8 for where it departs from the disabled code).
@@ -185,6 +189,40 @@ InitFlow initial_flow_of(const Value &im, const Value &args) {
   return f;
 }
 
+// build-only "consistency": false (default), true (alpha 0.01, beta 0.5) or {"alpha": a, "beta":
+// b}, per image or global: every ROI is also solved backward (the frame views swapped, a seed
+// negated), the forward flow is scored against the backward one (tvl1_fb_score) and
+// zeroed where !(score <= beta) after the post-process (tvl1_zero_above); random_points draws
+// "consistencyOversample" times as many candidates (default 4) and emits the first npoints that
+// are consistent; "consistencyOutput" writes the score plane as {output}{suffix}_fb.tiff.
+struct Consistency {
+  bool on = false;
+  float alpha = 0.01f, beta = 0.5f;
+  int oversample = 4;
+  bool output = false;
+};
+const char *const kConsistencyFeatures =
+    "consistency cannot be combined with feature alignment (features, a pair without ROIs, or "
+    "frames of different sizes): the backward pair would need the inverse alignment";
+Consistency consistency_of(const Value &im, const Value &args) {
+  Consistency c;
+  const Value &v = im.isMember("consistency") ? im["consistency"] : args["consistency"];
+  if (v.isObject()) {
+    c.on = true;
+    c.alpha = v.get("alpha", 0.01).asFloat();
+    c.beta = v.get("beta", 0.5).asFloat();
+  } else if (v.isNumeric()) {   // true / false; any other value of the key stays inert
+    c.on = v.asBool();
+  }
+  c.oversample = std::max(1, im.get("consistencyOversample", args.get("consistencyOversample", 4).asInt()).asInt());
+  c.output = im.get("consistencyOutput", args.get("consistencyOutput", false).asBool()).asBool();
+  return c;
+}
+void consistency_json(Value &dst, const Consistency &c) {
+  dst["alpha"] = (double)c.alpha;
+  dst["beta"] = (double)c.beta;
+}
+
 bool file_exists(const std::string &p) {
   struct stat st;
   return stat(p.c_str(), &st) == 0;
@@ -201,6 +239,9 @@ struct DeviceCtx {
   size_t cap_img = 0;
   float *du = nullptr, *dv = nullptr;
   size_t cap_flow = 0;
+  // "consistency": the backward flow and the score of the ROI being solved
+  float *dub = nullptr, *dvb = nullptr, *dsc = nullptr;
+  size_t cap_fb = 0;
   // frame reuse: the (name, scale) currently resident in d0 / d1
   std::string key0, key1;
   ofio::Image8 h0, h1;
@@ -369,6 +410,24 @@ bool ensure(DeviceCtx &dc, size_t img_bytes, size_t flow_bytes, bool &realloc, s
   return true;
 }
 
+// the three planes "consistency" adds, of the size of the largest ROI's flow
+bool ensure_fb(DeviceCtx &dc, size_t flow_bytes, std::string &err) {
+  if (flow_bytes <= dc.cap_fb) return true;
+  if (dc.stream) (void)hipStreamSynchronize(dc.stream);
+  for (float **b : {&dc.dub, &dc.dvb, &dc.dsc}) {
+    if (*b) (void)hipFree(*b);
+    *b = nullptr;
+  }
+  dc.cap_fb = 0;
+  if (hipMalloc((void **)&dc.dub, flow_bytes) != hipSuccess || hipMalloc((void **)&dc.dvb, flow_bytes) != hipSuccess ||
+      hipMalloc((void **)&dc.dsc, flow_bytes) != hipSuccess) {
+    err = "hipMalloc failed for the backward flow", dc.faulted = true;
+    return false;
+  }
+  dc.cap_fb = flow_bytes;
+  return true;
+}
+
 // The reference draws with glibc rand() after std::srand(time(0)) (or, with "debug",
 // from the unseeded default state = seed 1).  Other code in this process (the HIP
 // runtime) also consumes rand(), so use a PRIVATE generator with glibc's exact
@@ -419,9 +478,29 @@ void emit_points(const std::vector<std::pair<int, int>> &pts, const std::vector<
   }
 }
 
+// "consistency": of the candidates (px, their flow and score, in drawing order) keep the first
+// npoints with score <= beta; returns how many are kept
+size_t keep_consistent(std::vector<std::pair<int, int>> &pts, std::vector<float> &vx, std::vector<float> &vy,
+                       const std::vector<float> &sc, float beta, int npoints) {
+  size_t k = 0;
+  for (size_t i = 0; i < pts.size() && k < (size_t)std::max(npoints, 0); ++i)
+    if (sc[i] <= beta) {   // false for NaN and +inf
+      pts[k] = pts[i], vx[k] = vx[i], vy[k] = vy[i];
+      ++k;
+    }
+  pts.resize(k), vx.resize(k), vy.resize(k);
+  return k;
+}
+
+// how many candidates "consistency" draws for npoints points
+size_t candidates_of(int npoints, const Consistency *cons) {
+  return (size_t)std::max(npoints, 0) * (size_t)(cons ? cons->oversample : 1);
+}
+
 void random_points(const float *fx, const float *fy, int W, int H,
                    Value &im, const Value &args, const Rect &r0, const Rect &r1,
-                   const std::vector<uint8_t> &mask, bool features) {
+                   const std::vector<uint8_t> &mask, bool features, const float *score = nullptr,
+                   const Consistency *cons = nullptr, Value *cons_stats = nullptr) {
   const bool debug = args.get("debug", false).asBool();
   const float scale = im.get("scale", args.get("scale", 0.5).asFloat()).asFloat();
   const float inv_scale = 1. / scale;
@@ -438,13 +517,24 @@ void random_points(const float *fx, const float *fy, int W, int H,
       if (i != j) std::swap(loc[i], loc[j]);
     }
   }
-  std::vector<std::pair<int, int>> pts(loc.begin(), loc.begin() + std::min<size_t>(loc.size(), std::max(npoints, 0)));
+  // the first npoints of the shuffle; "consistency": the first npoints x oversample are the
+  // candidates
+  std::vector<std::pair<int, int>> pts(loc.begin(), loc.begin() + std::min<size_t>(loc.size(), candidates_of(npoints, cons)));
   std::vector<float> vx(pts.size()), vy(pts.size());
   for (size_t i = 0; i < pts.size(); ++i) {
     vx[i] = fx[(size_t)pts[i].second * W + pts[i].first];
     vy[i] = fy[(size_t)pts[i].second * W + pts[i].first];
   }
-  emit_points(pts, vx, vy, !loc.empty(), im, r0, r1, inv_scale, features);
+  bool any = !loc.empty();
+  if (cons) {
+    std::vector<float> sc(pts.size());
+    for (size_t i = 0; i < pts.size(); ++i) sc[i] = score[(size_t)pts[i].second * W + pts[i].first];
+    const size_t ncand = pts.size();
+    const size_t kept = keep_consistent(pts, vx, vy, sc, cons->beta, npoints);
+    any = kept > 0;
+    if (cons_stats) (*cons_stats)["candidates"] = (int64_t)ncand, (*cons_stats)["kept"] = (int64_t)kept;
+  }
+  emit_points(pts, vx, vy, any, im, r0, r1, inv_scale, features);
 }
 
 // An engine status that leaves the device context in doubt (a HIP call failed, memory ran
@@ -510,14 +600,15 @@ std::vector<std::pair<int, int>> sample_points(R0 row0, R1 row1, int W, int H, i
 // Debug runs keep the exact shuffle (random_points above) so their output is reproducible.
 bool random_points_sampled(DeviceCtx &dc, size_t fp, int W, int H, const ofio::Image8 &f0,
                            const ofio::Image8 &f1, const Rect &r0, const Rect &r1, Value &im,
-                           const Value &args, bool features, std::string &err) {
+                           const Value &args, bool features, std::string &err,
+                           const Consistency *cons = nullptr, Value *cons_stats = nullptr) {
   const float scale = im.get("scale", args.get("scale", 0.5).asFloat()).asFloat();
   const float inv_scale = 1. / scale;
   const int npoints = im.get("npoints", args.get("npoints", 25).asInt()).asInt();
   uint64_t total = 0;
-  const std::vector<std::pair<int, int>> pts = sample_points(
+  std::vector<std::pair<int, int>> pts = sample_points(
       [&](int y) { return f0.row(r0.y + y) + r0.x; }, [&](int y) { return f1.row(r1.y + y) + r1.x; },
-      W, H, npoints, &total);
+      W, H, (int)std::min<size_t>(candidates_of(npoints, cons), (size_t)INT32_MAX), &total);
   std::vector<float> vx(pts.size()), vy(pts.size());
   std::vector<int64_t> off(pts.size());
   for (size_t i = 0; i < pts.size(); ++i)
@@ -531,7 +622,22 @@ bool random_points_sampled(DeviceCtx &dc, size_t fp, int W, int H, const ofio::I
     err = std::string("flow read-back failed: ") + tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
     return false;
   }
-  emit_points(pts, vx, vy, total > 0, im, r0, r1, inv_scale, features);
+  bool any = total > 0;
+  if (cons) {   // the candidates' score: the same gather with the score plane as both planes
+    std::vector<float> sc(pts.size()), sc2(pts.size());
+    if (const tvl1_status s = tvl1_gather_flow(dc.ctx, dc.dsc, dc.dsc,
+                                               (int64_t)((size_t)(H - 1) * (fp / 4) + W), off.data(),
+                                               (int32_t)off.size(), sc.data(), sc2.data(), dc.stream);
+        s != TVL1_OK) {
+      err = std::string("score read-back failed: ") + tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
+      return false;
+    }
+    const size_t ncand = pts.size();
+    const size_t kept = keep_consistent(pts, vx, vy, sc, cons->beta, npoints);
+    any = kept > 0;
+    if (cons_stats) (*cons_stats)["candidates"] = (int64_t)ncand, (*cons_stats)["kept"] = (int64_t)kept;
+  }
+  emit_points(pts, vx, vy, any, im, r0, r1, inv_scale, features);
   return true;
 }
 
@@ -563,6 +669,13 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
   const int W = r0.width, H = r0.height;
   tvl1_params prm = generate_TV_args(im, args);
   InitFlow init = initial_flow_of(im, args);
+  const Consistency cons = consistency_of(im, args);
+  if (cons.on && features) {
+    err = kConsistencyFeatures;
+    return false;
+  }
+  uint64_t rejected = 0;
+  Value cons_points;   // random_points: candidates, kept
   if (const tvl1_status s = tvl1_set_params(dc.ctx, &prm); s != TVL1_OK) {
     err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
     return false;
@@ -624,6 +737,15 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
         sv["initial_flow_auto"]["count_zero"] = (int64_t)shift.count_zero;
       }
     }
+    if (cons.on) {
+      consistency_json(sv["consistency"], cons);
+      sv["consistency"]["px"] = (int64_t)W * H;
+      sv["consistency"]["rejected_px"] = (int64_t)rejected;
+      if (cons_points.isObject()) {
+        sv["consistency"]["candidates"] = cons_points["candidates"];
+        sv["consistency"]["kept"] = cons_points["kept"];
+      }
+    }
     res.stats["solves"].append(sv);
   };
   tvl1_status s;
@@ -647,6 +769,32 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
     err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
     return false;
   }
+  // "consistency": the backward solve (the views swapped, the seed negated: an "auto" pair is
+  // estimated once, forward), then the score of the raw flows
+  if (cons.on) {
+    if (!ensure_fb(dc, (size_t)W * H * sizeof(float), err)) return false;
+    if (init.on) {
+      const float nx = -init.dx, ny = -init.dy;
+      uint32_t bx, by;
+      memcpy(&bx, &nx, 4);
+      memcpy(&by, &ny, 4);
+      if (hipMemsetD32Async((hipDeviceptr_t)dc.dub, (int)bx, (size_t)W * H, dc.stream) != hipSuccess ||
+          hipMemsetD32Async((hipDeviceptr_t)dc.dvb, (int)by, (size_t)W * H, dc.stream) != hipSuccess) {
+        err = "initial flow fill failed", dc.faulted = true;
+        return false;
+      }
+      s = tvl1_calc_init(dc.ctx, b, pitch1, a, pitch, W, H, dc.dub, dc.dvb, fp, dc.dub, dc.dvb, fp, nullptr,
+                         dc.stream);
+    } else {
+      s = tvl1_calc(dc.ctx, b, pitch1, a, pitch, W, H, dc.dub, dc.dvb, fp, nullptr, dc.stream);
+    }
+    if (s == TVL1_OK)
+      s = tvl1_fb_score(dc.ctx, dc.du, dc.dv, fp, dc.dub, dc.dvb, fp, W, H, cons.alpha, dc.dsc, fp, dc.stream);
+    if (s != TVL1_OK) {
+      err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
+      return false;
+    }
+  }
   const std::string otype = output_type_of(im, args);
   // features: map = flow + grid -> warpAffine(identity) -> flow = map - grid (mode 2),
   // or the map itself (mode 1);
@@ -661,14 +809,29 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
     err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
     return false;
   }
+  // "consistency": zero the px that failed the check, after the post-process (the reference
+  // applies its own mask after the map add, optflow.cpp:468-473); the count arrives with it
+  if (cons.on) {
+    s = tvl1_zero_above(dc.ctx, dc.du, dc.dv, fp, dc.dsc, fp, W, H, cons.beta, &rejected, dc.stream);
+    if (s != TVL1_OK) {
+      err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
+      return false;
+    }
+  }
   const bool sampled = otype == "random_points" && !args.get("debug", false).asBool();
   if (sampled) {
     if (hipStreamSynchronize(dc.stream) != hipSuccess) {
       err = "solve failed", dc.faulted = true;
       return false;
     }
-    record();
-    return random_points_sampled(dc, fp, W, H, f0, f1, r0, r1, im, args, features, err);
+    if (!cons.on) {
+      record();
+      return random_points_sampled(dc, fp, W, H, f0, f1, r0, r1, im, args, features, err);
+    }
+    const bool ok = random_points_sampled(dc, fp, W, H, f0, f1, r0, r1, im, args, features, err, &cons,
+                                          &cons_points);
+    record();   // with the candidates and the kept points
+    return ok;
   }
   ofio::HostVec<float> fx((size_t)W * H), fy((size_t)W * H);   // pinned (PinnedPool)
   if (hipMemcpyAsync(fx.data(), dc.du, fx.size() * 4, hipMemcpyDeviceToHost, dc.stream) != hipSuccess ||
@@ -677,9 +840,28 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
     err = "flow download failed", dc.faulted = true;
     return false;
   }
-  record();
+  // the score plane: the exact shuffle's candidates read it, "consistencyOutput" writes it
+  ofio::HostVec<float> fs(cons.on && (cons.output || otype == "random_points") ? (size_t)W * H : 0);
+  if (fs.size() && (hipMemcpyAsync(fs.data(), dc.dsc, fs.size() * 4, hipMemcpyDeviceToHost, dc.stream) != hipSuccess ||
+                    hipStreamSynchronize(dc.stream) != hipSuccess)) {
+    err = "score download failed", dc.faulted = true;
+    return false;
+  }
+  if (!cons.on) record();
+  if (otype == "random_points") {
+    // mask = (frame0 > 1) | (frame1 > 1) on the ROIs (optflow.cpp:486-494)
+    std::vector<uint8_t> mask((size_t)W * H);
+    for (int y = 0; y < H; ++y)
+      for (int x = 0; x < W; ++x)
+        mask[(size_t)y * W + x] = (f0.row(r0.y + y)[r0.x + x] > 1) | (f1.row(r1.y + y)[r1.x + x] > 1);
+    if (cons.on)
+      random_points(fx.data(), fy.data(), W, H, im, args, r0, r1, mask, features, fs.data(), &cons, &cons_points);
+    else
+      random_points(fx.data(), fy.data(), W, H, im, args, r0, r1, mask, features);
+  }
+  if (cons.on) record();   // with the candidates and the kept points
+  const std::string base = im["output"].asString() + im["output_suffix"].asString();
   if (otype == "map" || otype == "flow") {
-    const std::string base = im["output"].asString() + im["output_suffix"].asString();
     std::string e;
     if (!ofio::write_tiff_f32(base + "_x.tiff", fx.data(), W, H, fp, e) ||
         !ofio::write_tiff_f32(base + "_y.tiff", fy.data(), W, H, fp, e)) {
@@ -687,13 +869,12 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
       return false;
     }
   }
-  if (otype == "random_points") {
-    // mask = (frame0 > 1) | (frame1 > 1) on the ROIs (optflow.cpp:486-494)
-    std::vector<uint8_t> mask((size_t)W * H);
-    for (int y = 0; y < H; ++y)
-      for (int x = 0; x < W; ++x)
-        mask[(size_t)y * W + x] = (f0.row(r0.y + y)[r0.x + x] > 1) | (f1.row(r1.y + y)[r1.x + x] > 1);
-    random_points(fx.data(), fy.data(), W, H, im, args, r0, r1, mask, features);
+  if (cons.on && cons.output) {
+    std::string e;
+    if (!ofio::write_tiff_f32(base + "_fb.tiff", fs.data(), W, H, fp, e)) {
+      err = e;
+      return false;
+    }
   }
   return true;
 }
@@ -797,13 +978,15 @@ void close_device(DeviceCtx &dc) {
   if (dc.stream) (void)hipStreamSynchronize(dc.stream);
   if (dc.ctx) tvl1_destroy(dc.ctx);
   if (dc.stream) (void)hipStreamDestroy(dc.stream);
-  for (void *ptr : {(void *)dc.d0, (void *)dc.d1, (void *)dc.dw, (void *)dc.du, (void *)dc.dv})
+  for (void *ptr : {(void *)dc.d0, (void *)dc.d1, (void *)dc.dw, (void *)dc.du, (void *)dc.dv,
+                    (void *)dc.dub, (void *)dc.dvb, (void *)dc.dsc})
     if (ptr) (void)hipFree(ptr);
   dc.ctx = nullptr;
   dc.stream = nullptr;
   dc.d0 = dc.d1 = dc.dw = nullptr;
   dc.du = dc.dv = nullptr;
-  dc.cap_img = dc.cap_flow = 0;
+  dc.dub = dc.dvb = dc.dsc = nullptr;
+  dc.cap_img = dc.cap_flow = dc.cap_fb = 0;
   dc.key0.clear();
   dc.key1.clear();
 }
@@ -837,6 +1020,12 @@ bool solve_rois(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1_in
   const bool seeded = initial_flow_of(im, args).on;
   if (seeded && features) {
     err = kInitFlowFeatures;
+    return false;
+  }
+  // nor is a pair whose flow is checked against the backward solve
+  const bool checked = consistency_of(im, args).on;
+  if (checked && features) {
+    err = kConsistencyFeatures;
     return false;
   }
   const std::string otype = output_type_of(im, args);
@@ -898,6 +1087,10 @@ bool solve_rois(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1_in
                           "features even though it wasn't selected.\n");
         if (seeded) {   // (no ROI, or frames of different sizes: the reference aligns these)
           err = kInitFlowFeatures;
+          return false;
+        }
+        if (checked) {
+          err = kConsistencyFeatures;
           return false;
         }
         if (!align_frame1(dc, f0, *f1p, f1_aligned, im, args, affine, err)) return false;
@@ -1050,6 +1243,9 @@ static int from_file(Value &args, bool plan_only) {
   for (size_t i = 0; i < n; ++i)
     if (initial_flow_of(images[i], args).on && resolve_features(images[i], args))
       return fail("pair " + std::to_string(i) + ": " + kInitFlowFeatures);
+  for (size_t i = 0; i < n; ++i)
+    if (consistency_of(images[i], args).on && resolve_features(images[i], args))
+      return fail("pair " + std::to_string(i) + ": " + kConsistencyFeatures);
 
   // build-only: shard pairs over several GPUs (contiguous chunks keep slice reuse)
   std::vector<int> devices;
@@ -1236,6 +1432,11 @@ static int from_file(Value &args, bool plan_only) {
             pl["initialFlow"][0] = (double)f0.dx;
             pl["initialFlow"][1] = (double)f0.dy;
           }
+          if (const Consistency cs = consistency_of(im, args); cs.on) {   // backward solve + score
+            consistency_json(pl["consistency"], cs);
+            pl["consistency"]["oversample"] = cs.oversample;
+            pl["consistency"]["output"] = cs.output;
+          }
           const tvl1_params tp = generate_TV_args(im, args);
           pl["tv"]["tau"] = tp.tau;
           pl["tv"]["lambda"] = tp.lambda;
@@ -1351,27 +1552,35 @@ static int from_file(Value &args, bool plan_only) {
     const int mode = otype == "map" ? 1 : 0;   // no features on this path
     // "seededStripBatch": the global seed of every pair of the batch (else none is seeded)
     const InitFlow ginit = initial_flow_of(Value(), args);
-    // device buffers (grown): the chunk's packed frames and flows of one ROI key
+    // "consistency": the global key (a per-image one sends its pair the per-pair way)
+    const Consistency gcons = consistency_of(Value(), args);
+    // device buffers (grown): the chunk's packed frames and flows of one ROI key; with
+    // "consistency" also the backward flows and the scores
     uint8_t *dP = nullptr, *dQ = nullptr;
     float *dU = nullptr, *dV = nullptr;
+    float *dUb = nullptr, *dVb = nullptr, *dS = nullptr;
     size_t cap_px = 0;
     uint8_t *hP = nullptr, *hQ = nullptr;   // page-locked packing buffers (reused)
     size_t cap_h = 0;
     auto release = [&] {
-      for (void *q : {(void *)dP, (void *)dQ, (void *)dU, (void *)dV})
+      for (void *q : {(void *)dP, (void *)dQ, (void *)dU, (void *)dV, (void *)dUb, (void *)dVb, (void *)dS})
         if (q) (void)hipFree(q);
       for (void *q : {(void *)hP, (void *)hQ})
         if (q) (void)hipHostFree(q);
-      dP = dQ = nullptr, dU = dV = nullptr, hP = hQ = nullptr;
+      dP = dQ = nullptr, dU = dV = nullptr, dUb = dVb = dS = nullptr, hP = hQ = nullptr;
       cap_px = cap_h = 0;
     };
     auto grow = [&](size_t px) {
       if (px > cap_px) {
-        for (void *q : {(void *)dP, (void *)dQ, (void *)dU, (void *)dV})
+        for (void *q : {(void *)dP, (void *)dQ, (void *)dU, (void *)dV, (void *)dUb, (void *)dVb, (void *)dS})
           if (q) (void)hipFree(q);
-        dP = dQ = nullptr, dU = dV = nullptr, cap_px = 0;
+        dP = dQ = nullptr, dU = dV = nullptr, dUb = dVb = dS = nullptr, cap_px = 0;
         if (hipMalloc((void **)&dP, px) != hipSuccess || hipMalloc((void **)&dQ, px) != hipSuccess ||
             hipMalloc((void **)&dU, 4 * px) != hipSuccess || hipMalloc((void **)&dV, 4 * px) != hipSuccess)
+          return false;
+        if (gcons.on && (hipMalloc((void **)&dUb, 4 * px) != hipSuccess ||
+                         hipMalloc((void **)&dVb, 4 * px) != hipSuccess ||
+                         hipMalloc((void **)&dS, 4 * px) != hipSuccess))
           return false;
         cap_px = px;
       }
@@ -1473,7 +1682,7 @@ static int from_file(Value &args, bool plan_only) {
         std::vector<std::vector<Value>> solves(nb);
         // debug random_points: the flows of every key, drawn pair by pair afterwards so the
         // unseeded generator is consumed in the per-pair path's order (pair, then key)
-        std::vector<std::vector<float>> dbg_fx(roi_keys.size()), dbg_fy(roi_keys.size());
+        std::vector<std::vector<float>> dbg_fx(roi_keys.size()), dbg_fy(roi_keys.size()), dbg_fs(roi_keys.size());
         auto fail = [&](const std::string &what, tvl1_status st) {
           e = what + (dc.ctx ? std::string(": ") + tvl1_last_error(dc.ctx) : std::string());
           dc.faulted = device_fault(st);
@@ -1531,8 +1740,10 @@ static int from_file(Value &args, bool plan_only) {
                 for (int b = b0; b < std::min(nb, b0 + per); ++b) {
                   const ofio::Image8 &a = items[b].p->bands[kk], &c = items[b].q->bands[kk];
                   const int np = items[b].im.get("npoints", args.get("npoints", 25).asInt()).asInt();
+                  // "consistency": oversample times as many, the candidates
+                  const int nc = (int)std::min<size_t>(candidates_of(np, gcons.on ? &gcons : nullptr), (size_t)INT32_MAX);
                   pts[b] = sample_points([&](int y) { return a.row(y); }, [&](int y) { return c.row(y); },
-                                         a.width, a.height, np, &tot[b]);
+                                         a.width, a.height, nc, &tot[b]);
                 }
               }));
           }
@@ -1560,9 +1771,35 @@ static int from_file(Value &args, bool plan_only) {
           else
             sc = tvl1_calc_batch_const_init(dc.ctx, nb, dP, W, px, dQ, W, px, W, h, seed_xy.data(), dU,
                                             dV, 4 * (size_t)W, 4 * px, st.data(), dc.stream);
+          // "consistency": the same strips solved backward (the frames swapped; a seed negated,
+          // an "auto" pair's taken from the record the forward call returned), the raw flows
+          // scored, and after the post-process the px that failed zeroed and counted
+          std::vector<uint64_t> rejected(nb, 0);
+          if (sc == TVL1_OK && gcons.on) {
+            const auto tb = Clock::now();
+            if (!seeded) {
+              sc = tvl1_calc_batch(dc.ctx, nb, dQ, W, px, dP, W, px, W, h, dUb, dVb, 4 * (size_t)W, 4 * px,
+                                   nullptr, dc.stream);
+            } else {
+              std::vector<float> back(2 * (size_t)nb);
+              for (int b = 0; b < nb; ++b) {
+                back[2 * b] = -(ginit.automatic ? (float)shifts[b].dx : ginit.dx);
+                back[2 * b + 1] = -(ginit.automatic ? (float)shifts[b].dy : ginit.dy);
+              }
+              sc = tvl1_calc_batch_const_init(dc.ctx, nb, dQ, W, px, dP, W, px, W, h, back.data(), dUb, dVb,
+                                              4 * (size_t)W, 4 * px, nullptr, dc.stream);
+            }
+            tm["solve_backward"] += secs_since(tb);
+            if (sc == TVL1_OK)
+              sc = tvl1_fb_score_batch(dc.ctx, nb, dU, dV, 4 * (size_t)W, 4 * px, dUb, dVb, 4 * (size_t)W,
+                                       4 * px, W, h, gcons.alpha, dS, 4 * (size_t)W, 4 * px, dc.stream);
+          }
           if (sc == TVL1_OK)
             sc = tvl1_postprocess_batch(dc.ctx, nb, dU, dV, 4 * (size_t)W, 4 * px, dQ, W, px, W, h,
                                         mode, dc.stream);
+          if (sc == TVL1_OK && gcons.on)
+            sc = tvl1_zero_above_batch(dc.ctx, nb, dU, dV, 4 * (size_t)W, 4 * px, dS, 4 * (size_t)W, 4 * px,
+                                       W, h, gcons.beta, rejected.data(), dc.stream);
           if (sc != TVL1_OK) {
             for (auto &f : draws) f.wait();   // they read this chunk's bands
             fail("strip batch", sc);
@@ -1575,6 +1812,7 @@ static int from_file(Value &args, bool plan_only) {
           }
           ts = Clock::now();
           std::vector<float> fx, fy;   // whole flows (TIFF outputs, debug point matches)
+          std::vector<float> fs;       // "consistency": the candidates' scores, or whole planes
           if (sampled) {
             for (auto &f : draws) f.wait();
             std::vector<int64_t> off;
@@ -1586,6 +1824,12 @@ static int from_file(Value &args, bool plan_only) {
             fy.resize(off.size());
             sc = tvl1_gather_flow(dc.ctx, dU, dV, (int64_t)(px * nb), off.data(), (int32_t)off.size(),
                                   fx.data(), fy.data(), dc.stream);
+            if (sc == TVL1_OK && gcons.on) {   // the score plane as both planes
+              fs.resize(off.size());
+              std::vector<float> fs2(off.size());
+              sc = tvl1_gather_flow(dc.ctx, dS, dS, (int64_t)(px * nb), off.data(), (int32_t)off.size(),
+                                    fs.data(), fs2.data(), dc.stream);
+            }
             if (sc != TVL1_OK) {
               fail("flow read-back", sc);
               break;
@@ -1598,6 +1842,14 @@ static int from_file(Value &args, bool plan_only) {
                 hipStreamSynchronize(dc.stream) != hipSuccess) {
               fail("flow download failed", TVL1_EHIP);
               break;
+            }
+            if (gcons.on && (gcons.output || otype == "random_points")) {
+              fs.resize(px * nb);
+              if (hipMemcpyAsync(fs.data(), dS, 4 * px * nb, hipMemcpyDeviceToHost, dc.stream) != hipSuccess ||
+                  hipStreamSynchronize(dc.stream) != hipSuccess) {
+                fail("score download failed", TVL1_EHIP);
+                break;
+              }
             }
           }
           const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -1634,12 +1886,39 @@ static int from_file(Value &args, bool plan_only) {
               }
             }
             sv["read_rows_only"] = items[b].p->partial && items[b].q->partial;
-            solves[b].push_back(sv);
+            if (gcons.on) {
+              consistency_json(sv["consistency"], gcons);
+              sv["consistency"]["px"] = (int64_t)px;
+              sv["consistency"]["rejected_px"] = (int64_t)rejected[b];
+            }
             if (sampled) {
               std::vector<float> vx(fx.begin() + o, fx.begin() + o + pts[b].size()),
                   vy(fy.begin() + o, fy.begin() + o + pts[b].size());
-              o += pts[b].size();
-              emit_points(pts[b], vx, vy, tot[b] > 0, im, r, r, 1.f / scale, false);
+              bool any = tot[b] > 0;
+              if (gcons.on) {
+                const std::vector<float> vs(fs.begin() + o, fs.begin() + o + pts[b].size());
+                const size_t ncand = pts[b].size();
+                o += ncand;
+                const int np = im.get("npoints", args.get("npoints", 25).asInt()).asInt();
+                const size_t kept = keep_consistent(pts[b], vx, vy, vs, gcons.beta, np);
+                any = kept > 0;
+                sv["consistency"]["candidates"] = (int64_t)ncand;
+                sv["consistency"]["kept"] = (int64_t)kept;
+              } else {
+                o += pts[b].size();
+              }
+              emit_points(pts[b], vx, vy, any, im, r, r, 1.f / scale, false);
+            }
+            solves[b].push_back(sv);
+            if (gcons.on && gcons.output && !sampled) {
+              std::string we;
+              if (!ofio::write_tiff_f32(im["output"].asString() + "_" + key + "_fb.tiff", fs.data() + px * b, W, h,
+                                        4 * (size_t)W, we)) {
+                e = we, ok = false;
+                dc.faulted = false;
+              }
+            }
+            if (sampled) {
             } else if (otype == "random_points") {   // debug: drawn below, pair by pair
             } else {
               const std::string base = im["output"].asString() + "_" + key;
@@ -1654,6 +1933,7 @@ static int from_file(Value &args, bool plan_only) {
           if (otype == "random_points" && !sampled) {
             dbg_fx[kk].swap(fx);
             dbg_fy[kk].swap(fy);
+            dbg_fs[kk].swap(fs);
           }
           tm["write_outputs"] += secs_since(ts);
         }
@@ -1671,8 +1951,13 @@ static int from_file(Value &args, bool plan_only) {
               const Rect r{0, roi_keys[kk] == "top" ? 0 : items[b].p->H - h, W, h};
               std::vector<uint8_t> mask(px);
               for (size_t k = 0; k < px; ++k) mask[k] = (a.data[k] > 1) | (c.data[k] > 1);
-              random_points(dbg_fx[kk].data() + px * b, dbg_fy[kk].data() + px * b, W, h,
-                            items[b].im, args, r, r, mask, false);
+              if (gcons.on)   // solves[b][kk]: this key's record, for the candidates and the kept
+                random_points(dbg_fx[kk].data() + px * b, dbg_fy[kk].data() + px * b, W, h, items[b].im,
+                              args, r, r, mask, false, dbg_fs[kk].data() + px * b, &gcons,
+                              &solves[b][kk]["consistency"]);
+              else
+                random_points(dbg_fx[kk].data() + px * b, dbg_fy[kk].data() + px * b, W, h,
+                              items[b].im, args, r, r, mask, false);
             }
         }
         if (ok) {

@@ -29,6 +29,7 @@
 #include "tvl1_align.hpp"
 #include "tvl1_stack.hpp"
 #include "tvl1_shift.hpp"
+#include "tvl1_fbcheck.hpp"
 
 // the iteration passes are compiled in tvl1_passes.hip (another instruction scheduler)
 namespace tvl1k {
@@ -190,6 +191,8 @@ struct tvl1_ctx {
   size_t shift_bytes = 0;
   char *seed_scratch = nullptr;         // tvl1_calc_batch_const_init / _auto_init: every pair's
   size_t seed_bytes = 0;                // constants (then two planes for pairs solved alone)
+  char *fb_counts = nullptr;            // tvl1_zero_above_batch's per-pair counters (a block of
+  size_t fb_bytes = 0;                  // its own: grown, never shrunk, no solver scratch)
   int bnblk = 0;                        // partials per pair
   int check = 0;             // TVL1_CHECK=1: synchronise + check after every launch (diagnostics)
 
@@ -3270,6 +3273,146 @@ tvl1_status tvl1_postprocess(tvl1_ctx *c, float *u, float *v, size_t fpitch, con
   return TVL1_OK;
 }
 
+// ---- Forward-backward consistency score (added under ABI 9; kernels in tvl1_fbcheck.hpp,
+// DESIGN 13) ----
+static constexpr int kFbChunk = 256;              // pairs per launch
+static constexpr int32_t kFbMaxDim = 1 << 24;     // float(x) is exact up to here
+
+// One f32 plane of each of n pairs: its span in bytes over the whole batch
+struct FbPlane {
+  const char *name;
+  const void *p;
+  size_t pitch, stride;
+};
+
+static bool fb_overlap(const FbPlane &a, const FbPlane &b, int32_t n, int32_t w, int32_t h) {
+  auto span = [&](const FbPlane &q, uintptr_t &lo, uintptr_t &hi) {
+    lo = reinterpret_cast<uintptr_t>(q.p);
+    hi = lo + (size_t)(n - 1) * q.stride + q.pitch * (size_t)(h - 1) + (size_t)w * sizeof(float);
+  };
+  uintptr_t a0, a1, b0, b1;
+  span(a, a0, a1);
+  span(b, b0, b1);
+  return a0 < b1 && b0 < a1;
+}
+
+// Everything tvl1_fb_score_batch and tvl1_zero_above_batch check about sizes and planes, before
+// anything is launched
+static tvl1_status check_fb(tvl1_ctx *c, int32_t n, int32_t w, int32_t h, const FbPlane *pl, int np) {
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  for (int i = 0; i < np; ++i)
+    if (!pl[i].p) return set_err(c, TVL1_EINVAL, "%s is NULL", pl[i].name);
+  if (n < 1) return set_err(c, TVL1_EINVAL, "n must be >= 1 (got %d)", n);
+  if (w < 1 || h < 1) return set_err(c, TVL1_EINVAL, "bad size %dx%d", w, h);
+  if (w > kFbMaxDim || h > kFbMaxDim)
+    return set_err(c, TVL1_ESIZE, "size %dx%d above 2^24 (float(x) is no longer exact)", w, h);
+  for (int i = 0; i < np; ++i) {
+    if (pl[i].pitch % 4 || pl[i].pitch < (size_t)w * sizeof(float))
+      return set_err(c, TVL1_EINVAL, "%s: pitch must be a multiple of 4 and >= 4 * w", pl[i].name);
+    if (pl[i].stride % 4)
+      return set_err(c, TVL1_EINVAL, "%s: pair stride must be a multiple of 4", pl[i].name);
+    if (n > 1 && pl[i].stride < pl[i].pitch * (size_t)(h - 1) + (size_t)w * sizeof(float))
+      return set_err(c, TVL1_EINVAL, "%s: pair stride must cover one plane", pl[i].name);
+  }
+  return TVL1_OK;
+}
+
+static inline dim3 fb_grid(int w, int h, int n) {
+  return dim3((unsigned)((w + 64 * kFbPx - 1) / (64 * kFbPx)), (unsigned)n,
+              (unsigned)std::min((h + 3) / 4, kFbMaxRowGroups));
+}
+
+tvl1_status tvl1_fb_score_batch(tvl1_ctx *c, int32_t n, const float *uf, const float *vf,
+                                size_t fpitch, size_t fstride, const float *ub, const float *vb,
+                                size_t bpitch, size_t bstride, int32_t w, int32_t h, float alpha,
+                                float *score, size_t spitch, size_t sstride, void *stream) {
+  const FbPlane pl[5] = {{"uf", uf, fpitch, fstride}, {"vf", vf, fpitch, fstride},
+                         {"ub", ub, bpitch, bstride}, {"vb", vb, bpitch, bstride},
+                         {"score", score, spitch, sstride}};
+  TVL1_TRY(check_fb(c, n, w, h, pl, 5));
+  if (std::isnan(alpha)) return set_err(c, TVL1_EINVAL, "alpha is NaN");
+  for (int i = 0; i < 4; ++i)
+    if (fb_overlap(pl[4], pl[i], n, w, h))
+      return set_err(c, TVL1_EINVAL, "score overlaps %s", pl[i].name);
+  for (int i = 0; i < 2; ++i)
+    for (int k = 2; k < 4; ++k)
+      if (fb_overlap(pl[i], pl[k], n, w, h))
+        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[k].name, pl[i].name);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t tok = xprof_begin(c, st);
+  for (int32_t b = 0; b < n; b += kFbChunk) {
+    const int m = std::min(kFbChunk, n - b);
+    FbScoreArgs a;
+    a.uf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(uf) + (size_t)b * fstride);
+    a.vf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vf) + (size_t)b * fstride);
+    a.ub = reinterpret_cast<const float *>(reinterpret_cast<const char *>(ub) + (size_t)b * bstride);
+    a.vb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vb) + (size_t)b * bstride);
+    a.score = reinterpret_cast<float *>(reinterpret_cast<char *>(score) + (size_t)b * sstride);
+    a.fp = fpitch, a.fs = fstride, a.bp = bpitch, a.bs = bstride, a.sp = spitch, a.ss = sstride;
+    a.w = w, a.h = h, a.alpha = alpha;
+    hipLaunchKernelGGL(k_fb_score, fb_grid(w, h, m), kBlk2, 0, st, a);
+  }
+  xprof_end(c, st, tok, 20.0 * w * h * n);
+  HIP_TRY(c, hipGetLastError());
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_fb_score(tvl1_ctx *c, const float *uf, const float *vf, size_t fpitch,
+                          const float *ub, const float *vb, size_t bpitch, int32_t w, int32_t h,
+                          float alpha, float *score, size_t spitch, void *stream) {
+  return tvl1_fb_score_batch(c, 1, uf, vf, fpitch, 0, ub, vb, bpitch, 0, w, h, alpha, score, spitch, 0,
+                             stream);
+}
+
+tvl1_status tvl1_zero_above_batch(tvl1_ctx *c, int32_t n, float *u, float *v, size_t fpitch,
+                                  size_t fstride, const float *score, size_t spitch, size_t sstride,
+                                  int32_t w, int32_t h, float beta, uint64_t *rejected,
+                                  void *stream) {
+  const FbPlane pl[3] = {{"u", u, fpitch, fstride}, {"v", v, fpitch, fstride},
+                         {"score", score, spitch, sstride}};
+  TVL1_TRY(check_fb(c, n, w, h, pl, 3));
+  if (std::isnan(beta)) return set_err(c, TVL1_EINVAL, "beta is NaN");
+  for (int i = 0; i < 2; ++i)
+    if (fb_overlap(pl[2], pl[i], n, w, h))
+      return set_err(c, TVL1_EINVAL, "score overlaps %s", pl[i].name);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long *cnt = nullptr;
+  if (rejected) {
+    order_streams(c, st);
+    if (!c->retired.empty()) reap_retired(c, false);
+    const size_t need = kFbChunk * sizeof(unsigned long long);
+    if (need > c->fb_bytes) TVL1_TRY(arena_alloc(c, &c->fb_counts, &c->fb_bytes, need, st));
+    cnt = reinterpret_cast<unsigned long long *>(c->fb_counts);
+  }
+  const size_t tok = xprof_begin(c, st);
+  for (int32_t b = 0; b < n; b += kFbChunk) {
+    const int m = std::min(kFbChunk, n - b);
+    // the next chunk's zero fill is in stream order behind this one's copy
+    if (cnt) HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(unsigned long long), st));
+    ZeroAboveArgs a;
+    a.u = reinterpret_cast<float *>(reinterpret_cast<char *>(u) + (size_t)b * fstride);
+    a.v = reinterpret_cast<float *>(reinterpret_cast<char *>(v) + (size_t)b * fstride);
+    a.score = reinterpret_cast<const float *>(reinterpret_cast<const char *>(score) + (size_t)b * sstride);
+    a.fp = fpitch, a.fs = fstride, a.sp = spitch, a.ss = sstride;
+    a.w = w, a.h = h, a.beta = beta, a.count = cnt;
+    hipLaunchKernelGGL(k_zero_above, fb_grid(w, h, m), kBlk2, 0, st, a);
+    if (cnt)
+      HIP_TRY(c, hipMemcpyAsync(rejected + b, cnt, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  }
+  xprof_end(c, st, tok, 12.0 * w * h * n);
+  HIP_TRY(c, hipGetLastError());
+  if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_zero_above(tvl1_ctx *c, float *u, float *v, size_t fpitch, const float *score,
+                            size_t spitch, int32_t w, int32_t h, float beta, uint64_t *rejected,
+                            void *stream) {
+  return tvl1_zero_above_batch(c, 1, u, v, fpitch, 0, score, spitch, 0, w, h, beta, rejected, stream);
+}
+
 void *tvl1_stream(tvl1_ctx *c) { return c ? (void *)c->own_stream : nullptr; }
 
 tvl1_status tvl1_set_profiling(tvl1_ctx *c, int32_t enable) {
@@ -3297,6 +3440,7 @@ void tvl1_destroy(tvl1_ctx *c) {
   if (c->small_scratch) (void)hipFree(c->small_scratch);
   if (c->shift_scratch) (void)hipFree(c->shift_scratch);
   if (c->seed_scratch) (void)hipFree(c->seed_scratch);
+  if (c->fb_counts) (void)hipFree(c->fb_counts);
   for (auto &r : c->retired) free_retired(r);
   if (c->align_pat) (void)hipFree(c->align_pat);
   if (c->pinned) (void)hipHostFree(c->pinned);

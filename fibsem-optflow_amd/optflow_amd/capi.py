@@ -290,6 +290,24 @@ def load_engine() -> C.CDLL:
                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p]
     lib.tvl1_sad_shifts_u8.restype = C.c_int
+    # forward-backward consistency score (added under ABI 9)
+    lib.tvl1_fb_score_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                        C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_size_t,
+                                        C.c_size_t, C.c_void_p]
+    lib.tvl1_fb_score_batch.restype = C.c_int
+    lib.tvl1_fb_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_float,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tvl1_fb_score.restype = C.c_int
+    lib.tvl1_zero_above_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int32,
+                                          C.c_int32, C.c_float, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.tvl1_zero_above_batch.restype = C.c_int
+    lib.tvl1_zero_above.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.c_size_t, C.c_int32, C.c_int32, C.c_float,
+                                    C.POINTER(C.c_uint64), C.c_void_p]
+    lib.tvl1_zero_above.restype = C.c_int
     lib.tvl1_stream.argtypes = [C.c_void_p]
     lib.tvl1_stream.restype = C.c_void_p
     lib.tvl1_set_profiling.argtypes = [C.c_void_p, C.c_int32]
@@ -680,6 +698,84 @@ class Engine:
         torch.cuda.synchronize()
         return self.estimate_shift(d0.data_ptr(), w, d1.data_ptr(), w, w, h, max_shift,
                                    stream=self.stream)
+
+    # ---- forward-backward consistency score (tvl1_fb_score ... tvl1_zero_above_batch) ----
+    def fb_score_batch(self, n: int, duf: int, dvf: int, f_pitch: int, f_stride: int, dub: int,
+                       dvb: int, b_pitch: int, b_stride: int, w: int, h: int, alpha: float,
+                       dscore: int, s_pitch: int, s_stride: int, stream: int = 0) -> None:
+        """tvl1_fb_score_batch on device f32 planes (pitches and pair strides in bytes): the
+        score of n pairs' forward flows (uf, vf) against their backward flows (ub, vb)."""
+        self._check(self.lib.tvl1_fb_score_batch(
+            self.ctx, n, C.c_void_p(duf or None), C.c_void_p(dvf or None), f_pitch, f_stride,
+            C.c_void_p(dub or None), C.c_void_p(dvb or None), b_pitch, b_stride, w, h, float(alpha),
+            C.c_void_p(dscore or None), s_pitch, s_stride, C.c_void_p(stream) if stream else None),
+            "tvl1_fb_score_batch")
+
+    def fb_score(self, duf: int, dvf: int, f_pitch: int, dub: int, dvb: int, b_pitch: int, w: int,
+                 h: int, alpha: float, dscore: int, s_pitch: int, stream: int = 0) -> None:
+        """tvl1_fb_score: one pair."""
+        self._check(self.lib.tvl1_fb_score(
+            self.ctx, C.c_void_p(duf or None), C.c_void_p(dvf or None), f_pitch,
+            C.c_void_p(dub or None), C.c_void_p(dvb or None), b_pitch, w, h, float(alpha),
+            C.c_void_p(dscore or None), s_pitch, C.c_void_p(stream) if stream else None),
+            "tvl1_fb_score")
+
+    def zero_above_batch(self, n: int, du: int, dv: int, f_pitch: int, f_stride: int, dscore: int,
+                         s_pitch: int, s_stride: int, w: int, h: int, beta: float,
+                         stream: int = 0, count: bool = True):
+        """tvl1_zero_above_batch: u = v = 0 where !(score <= beta), in place.  Returns the
+        rejected px of each pair (uint64 array of n), or None with count=False (the call then
+        stays asynchronous)."""
+        rej = np.zeros(max(1, n), np.uint64) if count else None
+        self._check(self.lib.tvl1_zero_above_batch(
+            self.ctx, n, C.c_void_p(du or None), C.c_void_p(dv or None), f_pitch, f_stride,
+            C.c_void_p(dscore or None), s_pitch, s_stride, w, h, float(beta),
+            rej.ctypes.data_as(C.POINTER(C.c_uint64)) if count else None,
+            C.c_void_p(stream) if stream else None), "tvl1_zero_above_batch")
+        return rej[:max(0, n)] if count else None
+
+    def zero_above(self, du: int, dv: int, f_pitch: int, dscore: int, s_pitch: int, w: int, h: int,
+                   beta: float, stream: int = 0) -> int:
+        """tvl1_zero_above: one pair; returns its rejected px."""
+        rej = C.c_uint64(0)
+        self._check(self.lib.tvl1_zero_above(
+            self.ctx, C.c_void_p(du or None), C.c_void_p(dv or None), f_pitch,
+            C.c_void_p(dscore or None), s_pitch, w, h, float(beta), C.byref(rej),
+            C.c_void_p(stream) if stream else None), "tvl1_zero_above")
+        return int(rej.value)
+
+    def calc_consistent(self, I0: np.ndarray, I1: np.ndarray, alpha: float = 0.01,
+                        beta: float = 0.5, init=None):
+        """Forward solve I0 -> I1, backward solve I1 -> I0 (the frames swapped), their score,
+        and the forward flow zeroed where !(score <= beta).  Host u8 arrays of one size in;
+        returns (u, v, score, rejected): float32 arrays and the number of zeroed px.  init =
+        (dx, dy): both solves start from a constant flow (tvl1_calc_batch_const_init), the
+        forward one from (dx, dy), the backward one from (-dx, -dy)."""
+        import torch
+        I0 = np.array(I0, dtype=np.uint8, order="C")   # copies: torch wants writable arrays
+        I1 = np.array(I1, dtype=np.uint8, order="C")
+        if I1.shape != I0.shape:
+            raise ValueError("I0 and I1 must have the same size")
+        h, w = I0.shape
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d0, d1 = torch.from_numpy(I0).to(dev), torch.from_numpy(I1).to(dev)
+        fl = torch.zeros((5, h, w), dtype=torch.float32, device=dev)   # uf, vf, ub, vb, score
+        torch.cuda.synchronize()
+        st = self.stream
+        p = [fl[k].data_ptr() for k in range(5)]
+        for (a, b, pu, pv, sign) in ((d0, d1, p[0], p[1], 1.0), (d1, d0, p[2], p[3], -1.0)):
+            if init is None:
+                self.calc_device(a.data_ptr(), w, b.data_ptr(), w, w, h, pu, pv, 4 * w, stream=st,
+                                 stats=False)
+            else:
+                seed = np.array([[sign * float(init[0]), sign * float(init[1])]], np.float32)
+                self.calc_batch_device(1, a.data_ptr(), w, w * h, b.data_ptr(), w, w * h, w, h,
+                                       pu, pv, 4 * w, 4 * w * h, stream=st, init_const=seed)
+        self.fb_score(p[0], p[1], 4 * w, p[2], p[3], 4 * w, w, h, alpha, p[4], 4 * w, stream=st)
+        rejected = self.zero_above(p[0], p[1], 4 * w, p[4], 4 * w, w, h, beta, stream=st)
+        torch.cuda.synchronize()
+        out = fl.cpu().numpy()
+        return out[0], out[1], out[4], rejected
 
     def close(self):
         if self.ctx:

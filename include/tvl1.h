@@ -442,6 +442,60 @@ tvl1_status tvl1_gather_flow(tvl1_ctx *ctx, const float *u, const float *v, int6
                              const int64_t *offsets, int32_t n, float *out_u, float *out_v,
                              void *stream);
 
+/* ---- Forward-backward consistency score (added under ABI 9) ----
+ * Given the forward flow (uf, vf) of a pair I0 -> I1 and the backward flow (ub, vb) of I1 -> I0
+ * (the same solve with the frames swapped), a px (x, y) follows its forward flow, reads the
+ * backward flow where it lands and scores how far the two are from cancelling.  Per px, every
+ * operation one IEEE f32 rounding in this order, never contracted, whatever the ctx's fast_math
+ * or profile:
+ *   X = float(x) + uf, Y = float(y) + vf;
+ *   unless 0 <= X <= float(w - 1) and 0 <= Y <= float(h - 1) (false for NaN): score = +inf;
+ *   x0 = int(floorf(X)), ax = X - float(x0), x1 = min(x0 + 1, w - 1); y0, ay, y1 likewise;
+ *   for P = ub, vb:  t = P[y0][x0] + ax * (P[y0][x1] - P[y0][x0]),
+ *                    b = P[y1][x0] + ax * (P[y1][x1] - P[y1][x0]),  s = t + ay * (b - t);
+ *   ex = uf + ubs, ey = vf + vbs, err = ex * ex + ey * ey;
+ *   mag = (uf * uf + vf * vf) + (ubs * ubs + vbs * vbs);  score = err - alpha * mag.
+ * A px is consistent at beta iff score <= beta (NaN and +inf are not): the usual
+ * |f + b(x + f)|^2 <= alpha (|f|^2 + |b(x + f)|^2) + beta with the threshold kept out of the
+ * plane, so one score plane serves any beta and can be gathered at points (tvl1_gather_flow).
+ *
+ * All planes are device f32, w x h, ROI views allowed: any pointer and any pitch that are
+ * multiples of 4.  Pair b's planes lie at base + b * pair stride (bytes); up to 256 pairs share
+ * a launch, a larger n is chunked.  Asynchronous on `stream`; no solver scratch is touched; with
+ * profiling on the calls count into class 2 of the ctx's next solve, as the slice-list calls do.
+ * TVL1_EINVAL before anything is launched: a null plane, n < 1, w or h < 1, a pitch below 4 w or
+ * not a multiple of 4, a pair stride that is not a multiple of 4 or (n > 1) does not cover one
+ * plane, NaN alpha or beta, score overlapping a flow plane, ub / vb overlapping uf / vf (overlap
+ * is judged on each plane's whole span over the n pairs).  TVL1_ESIZE: w or h above 2^24, where
+ * float(x) is no longer exact. */
+tvl1_status tvl1_fb_score_batch(tvl1_ctx *ctx, int32_t n,
+                                const float *uf, const float *vf, size_t f_pitch, size_t f_pair_stride,
+                                const float *ub, const float *vb, size_t b_pitch, size_t b_pair_stride,
+                                int32_t w, int32_t h, float alpha,
+                                float *score, size_t score_pitch, size_t score_pair_stride,
+                                void *stream);
+
+/* tvl1_fb_score_batch with n = 1. */
+tvl1_status tvl1_fb_score(tvl1_ctx *ctx, const float *uf, const float *vf, size_t f_pitch,
+                          const float *ub, const float *vb, size_t b_pitch, int32_t w, int32_t h,
+                          float alpha, float *score, size_t score_pitch, void *stream);
+
+/* u = v = 0 wherever !(score <= beta), in place: the I1 <= 1 mask's sibling, to run where that
+ * mask runs (after tvl1_postprocess, so a rejected px is 0 in "map" output too).  rejected: NULL,
+ * or n HOST values, the number of such px of each pair; the call then returns after the counts
+ * have arrived (it synchronizes the stream).  The per-pair counters live in a ctx block of their
+ * own. */
+tvl1_status tvl1_zero_above_batch(tvl1_ctx *ctx, int32_t n,
+                                  float *u, float *v, size_t flow_pitch, size_t flow_pair_stride,
+                                  const float *score, size_t score_pitch, size_t score_pair_stride,
+                                  int32_t w, int32_t h, float beta, uint64_t *rejected,
+                                  void *stream);
+
+/* tvl1_zero_above_batch with n = 1. */
+tvl1_status tvl1_zero_above(tvl1_ctx *ctx, float *u, float *v, size_t flow_pitch,
+                            const float *score, size_t score_pitch, int32_t w, int32_t h,
+                            float beta, uint64_t *rejected, void *stream);
+
 /* The ctx's own non-blocking HIP stream (hipStream_t as void*): callers that keep
  * several pairs in flight on one device give each ctx its own stream this way. */
 void *tvl1_stream(tvl1_ctx *ctx);
