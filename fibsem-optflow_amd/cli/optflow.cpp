@@ -46,7 +46,10 @@
 //     ROI is also solved backward, the forward flow is scored against the backward one and
 //     zeroed where the forward-backward check fails), "consistencyOversample"
 //     (random_points candidates per point, default 4) and "consistencyOutput" (the score plane
-//     as {output}{suffix}_fb.tiff);
+//     as {output}{suffix}_fb.tiff); "zncc" (false, true or {"radius", "beta"}: style 1 only; the
+//     one-solve check: each ROI's raw flow is scored by 1 - ZNCC of a window of frame0 against
+//     frame1 warped back along the flow and zeroed where score > beta; not together
+//     with "consistency"), "znccOversample" and "znccOutput" ({output}{suffix}_zncc.tiff);
 //   * "style": 2 (from_list below): the average-flow alignment of a slice list that the
 //     reference declares and keeps disabled; keys "slices" | "file_list", "border",
 //     "save_flow" (DESIGN 11, and 8 for where it departs from the disabled code).
@@ -200,6 +203,7 @@ struct Consistency {
   float alpha = 0.01f, beta = 0.5f;
   int oversample = 4;
   bool output = false;
+  int radius = 0;   // 1..4: the check is "zncc" (below), scored without a backward solve
 };
 const char *const kConsistencyFeatures =
     "consistency cannot be combined with feature alignment (features, a pair without ROIs, or "
@@ -219,9 +223,52 @@ Consistency consistency_of(const Value &im, const Value &args) {
   return c;
 }
 void consistency_json(Value &dst, const Consistency &c) {
-  dst["alpha"] = (double)c.alpha;
+  if (c.radius)
+    dst["radius"] = c.radius;
+  else
+    dst["alpha"] = (double)c.alpha;
   dst["beta"] = (double)c.beta;
 }
+
+// build-only "zncc": false (default), true (radius 3, beta 0.25) or {"radius": r, "beta": b}, per
+// image or global: the one-solve check.  Every ROI's raw flow is scored by 1 - ZNCC of a (2r+1)^2
+// window of frame0 against frame1 warped back along the flow (tvl1_zncc_score), on
+// the views the solve saw; from there on the score is used as "consistency" uses its own: the
+// flow is zeroed where !(score <= beta) after the post-process, random_points draws
+// "znccOversample" times as many candidates (default 4) and emits the first npoints with score
+// <= beta, "znccOutput" writes the score plane as {output}{suffix}_zncc.tiff.  It travels as a
+// Consistency with radius set.
+const char *const kZnccFeatures =
+    "zncc cannot be combined with feature alignment (features, a pair without ROIs, or frames of "
+    "different sizes): the score plane would need the alignment's warp";
+const char *const kZnccConsistency = "zncc cannot be combined with consistency";
+Consistency zncc_of(const Value &im, const Value &args) {
+  Consistency c;
+  c.radius = 3, c.beta = 0.25f;
+  const Value &v = im.isMember("zncc") ? im["zncc"] : args["zncc"];
+  if (v.isObject()) {
+    c.on = true;
+    c.radius = v.get("radius", 3).asInt();
+    c.beta = v.get("beta", 0.25).asFloat();
+  } else if (v.isNumeric()) {   // true / false; any other value of the key stays inert
+    c.on = v.asBool();
+  }
+  c.oversample = std::max(1, im.get("znccOversample", args.get("znccOversample", 4).asInt()).asInt());
+  c.output = im.get("znccOutput", args.get("znccOutput", false).asBool()).asBool();
+  return c;
+}
+// The check of a pair's flows: "consistency", "zncc" (radius set) or none; *err where the keys
+// cannot run as written
+Consistency check_of(const Value &im, const Value &args, const char **err = nullptr) {
+  const Consistency fb = consistency_of(im, args), zn = zncc_of(im, args);
+  if (err) *err = nullptr;
+  if (!zn.on) return fb;
+  if (err && fb.on) *err = kZnccConsistency;
+  if (err && !*err && (zn.radius < 1 || zn.radius > 4)) *err = "zncc: radius must be 1..4";
+  return zn;
+}
+const char *check_key(const Consistency &c) { return c.radius ? "zncc" : "consistency"; }
+const char *features_error(const Consistency &c) { return c.radius ? kZnccFeatures : kConsistencyFeatures; }
 
 bool file_exists(const std::string &p) {
   struct stat st;
@@ -669,9 +716,14 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
   const int W = r0.width, H = r0.height;
   tvl1_params prm = generate_TV_args(im, args);
   InitFlow init = initial_flow_of(im, args);
-  const Consistency cons = consistency_of(im, args);
+  const char *cons_err = nullptr;
+  const Consistency cons = check_of(im, args, &cons_err);   // "consistency" or "zncc"
+  if (cons_err) {
+    err = cons_err;
+    return false;
+  }
   if (cons.on && features) {
-    err = kConsistencyFeatures;
+    err = features_error(cons);
     return false;
   }
   uint64_t rejected = 0;
@@ -738,12 +790,13 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
       }
     }
     if (cons.on) {
-      consistency_json(sv["consistency"], cons);
-      sv["consistency"]["px"] = (int64_t)W * H;
-      sv["consistency"]["rejected_px"] = (int64_t)rejected;
+      Value &cv = sv[check_key(cons)];
+      consistency_json(cv, cons);
+      cv["px"] = (int64_t)W * H;
+      cv["rejected_px"] = (int64_t)rejected;
       if (cons_points.isObject()) {
-        sv["consistency"]["candidates"] = cons_points["candidates"];
-        sv["consistency"]["kept"] = cons_points["kept"];
+        cv["candidates"] = cons_points["candidates"];
+        cv["kept"] = cons_points["kept"];
       }
     }
     res.stats["solves"].append(sv);
@@ -771,7 +824,14 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
   }
   // "consistency": the backward solve (the views swapped, the seed negated: an "auto" pair is
   // estimated once, forward), then the score of the raw flows
-  if (cons.on) {
+  if (cons.on && cons.radius) {   // "zncc": one call on the views the solve saw and the raw flow
+    if (!ensure_fb(dc, (size_t)W * H * sizeof(float), err)) return false;
+    s = tvl1_zncc_score(dc.ctx, a, pitch, b, pitch1, dc.du, dc.dv, fp, W, H, cons.radius, dc.dsc, fp, dc.stream);
+    if (s != TVL1_OK) {
+      err = tvl1_last_error(dc.ctx), dc.faulted = device_fault(s);
+      return false;
+    }
+  } else if (cons.on) {
     if (!ensure_fb(dc, (size_t)W * H * sizeof(float), err)) return false;
     if (init.on) {
       const float nx = -init.dx, ny = -init.dy;
@@ -871,7 +931,7 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
   }
   if (cons.on && cons.output) {
     std::string e;
-    if (!ofio::write_tiff_f32(base + "_fb.tiff", fs.data(), W, H, fp, e)) {
+    if (!ofio::write_tiff_f32(base + (cons.radius ? "_zncc.tiff" : "_fb.tiff"), fs.data(), W, H, fp, e)) {
       err = e;
       return false;
     }
@@ -1023,9 +1083,15 @@ bool solve_rois(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1_in
     return false;
   }
   // nor is a pair whose flow is checked against the backward solve
-  const bool checked = consistency_of(im, args).on;
+  const char *check_err = nullptr;
+  const Consistency check = check_of(im, args, &check_err);
+  const bool checked = check.on;
+  if (check_err) {
+    err = check_err;
+    return false;
+  }
   if (checked && features) {
-    err = kConsistencyFeatures;
+    err = features_error(check);
     return false;
   }
   const std::string otype = output_type_of(im, args);
@@ -1090,7 +1156,7 @@ bool solve_rois(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1_in
           return false;
         }
         if (checked) {
-          err = kConsistencyFeatures;
+          err = features_error(check);
           return false;
         }
         if (!align_frame1(dc, f0, *f1p, f1_aligned, im, args, affine, err)) return false;
@@ -1243,9 +1309,13 @@ static int from_file(Value &args, bool plan_only) {
   for (size_t i = 0; i < n; ++i)
     if (initial_flow_of(images[i], args).on && resolve_features(images[i], args))
       return fail("pair " + std::to_string(i) + ": " + kInitFlowFeatures);
-  for (size_t i = 0; i < n; ++i)
-    if (consistency_of(images[i], args).on && resolve_features(images[i], args))
-      return fail("pair " + std::to_string(i) + ": " + kConsistencyFeatures);
+  for (size_t i = 0; i < n; ++i) {
+    const char *ce = nullptr;
+    const Consistency ck = check_of(images[i], args, &ce);
+    if (ce) return fail("pair " + std::to_string(i) + ": " + ce);
+    if (ck.on && resolve_features(images[i], args))
+      return fail("pair " + std::to_string(i) + ": " + features_error(ck));
+  }
 
   // build-only: shard pairs over several GPUs (contiguous chunks keep slice reuse)
   std::vector<int> devices;
@@ -1432,10 +1502,11 @@ static int from_file(Value &args, bool plan_only) {
             pl["initialFlow"][0] = (double)f0.dx;
             pl["initialFlow"][1] = (double)f0.dy;
           }
-          if (const Consistency cs = consistency_of(im, args); cs.on) {   // backward solve + score
-            consistency_json(pl["consistency"], cs);
-            pl["consistency"]["oversample"] = cs.oversample;
-            pl["consistency"]["output"] = cs.output;
+          if (const Consistency cs = check_of(im, args); cs.on) {   // (backward solve +) score
+            Value &cv = pl[check_key(cs)];
+            consistency_json(cv, cs);
+            cv["oversample"] = cs.oversample;
+            cv["output"] = cs.output;
           }
           const tvl1_params tp = generate_TV_args(im, args);
           pl["tv"]["tau"] = tp.tau;
@@ -1553,7 +1624,7 @@ static int from_file(Value &args, bool plan_only) {
     // "seededStripBatch": the global seed of every pair of the batch (else none is seeded)
     const InitFlow ginit = initial_flow_of(Value(), args);
     // "consistency": the global key (a per-image one sends its pair the per-pair way)
-    const Consistency gcons = consistency_of(Value(), args);
+    const Consistency gcons = check_of(Value(), args);   // or "zncc": one score call, no backward solve
     // device buffers (grown): the chunk's packed frames and flows of one ROI key; with
     // "consistency" also the backward flows and the scores
     uint8_t *dP = nullptr, *dQ = nullptr;
@@ -1578,10 +1649,10 @@ static int from_file(Value &args, bool plan_only) {
         if (hipMalloc((void **)&dP, px) != hipSuccess || hipMalloc((void **)&dQ, px) != hipSuccess ||
             hipMalloc((void **)&dU, 4 * px) != hipSuccess || hipMalloc((void **)&dV, 4 * px) != hipSuccess)
           return false;
-        if (gcons.on && (hipMalloc((void **)&dUb, 4 * px) != hipSuccess ||
-                         hipMalloc((void **)&dVb, 4 * px) != hipSuccess ||
-                         hipMalloc((void **)&dS, 4 * px) != hipSuccess))
+        if (gcons.on && !gcons.radius && (hipMalloc((void **)&dUb, 4 * px) != hipSuccess ||
+                                          hipMalloc((void **)&dVb, 4 * px) != hipSuccess))
           return false;
+        if (gcons.on && hipMalloc((void **)&dS, 4 * px) != hipSuccess) return false;
         cap_px = px;
       }
       if (px > cap_h) {
@@ -1775,7 +1846,15 @@ static int from_file(Value &args, bool plan_only) {
           // an "auto" pair's taken from the record the forward call returned), the raw flows
           // scored, and after the post-process the px that failed zeroed and counted
           std::vector<uint64_t> rejected(nb, 0);
-          if (sc == TVL1_OK && gcons.on) {
+          if (sc == TVL1_OK && gcons.on && gcons.radius) {
+            // "zncc": the packed strips and their raw flows scored in one call; a seed changes
+            // nothing here.  The stage is timed to the score's end on the stream.
+            const auto tz = Clock::now();
+            sc = tvl1_zncc_score_batch(dc.ctx, nb, dP, W, px, dQ, W, px, dU, dV, 4 * (size_t)W, 4 * px, W, h,
+                                       gcons.radius, dS, 4 * (size_t)W, 4 * px, dc.stream);
+            if (sc == TVL1_OK && hipStreamSynchronize(dc.stream) != hipSuccess) sc = TVL1_EHIP;
+            tm["zncc_score"] += secs_since(tz);
+          } else if (sc == TVL1_OK && gcons.on) {
             const auto tb = Clock::now();
             if (!seeded) {
               sc = tvl1_calc_batch(dc.ctx, nb, dQ, W, px, dP, W, px, W, h, dUb, dVb, 4 * (size_t)W, 4 * px,
@@ -1887,9 +1966,10 @@ static int from_file(Value &args, bool plan_only) {
             }
             sv["read_rows_only"] = items[b].p->partial && items[b].q->partial;
             if (gcons.on) {
-              consistency_json(sv["consistency"], gcons);
-              sv["consistency"]["px"] = (int64_t)px;
-              sv["consistency"]["rejected_px"] = (int64_t)rejected[b];
+              Value &cv = sv[check_key(gcons)];
+              consistency_json(cv, gcons);
+              cv["px"] = (int64_t)px;
+              cv["rejected_px"] = (int64_t)rejected[b];
             }
             if (sampled) {
               std::vector<float> vx(fx.begin() + o, fx.begin() + o + pts[b].size()),
@@ -1902,8 +1982,8 @@ static int from_file(Value &args, bool plan_only) {
                 const int np = im.get("npoints", args.get("npoints", 25).asInt()).asInt();
                 const size_t kept = keep_consistent(pts[b], vx, vy, vs, gcons.beta, np);
                 any = kept > 0;
-                sv["consistency"]["candidates"] = (int64_t)ncand;
-                sv["consistency"]["kept"] = (int64_t)kept;
+                sv[check_key(gcons)]["candidates"] = (int64_t)ncand;
+                sv[check_key(gcons)]["kept"] = (int64_t)kept;
               } else {
                 o += pts[b].size();
               }
@@ -1912,7 +1992,7 @@ static int from_file(Value &args, bool plan_only) {
             solves[b].push_back(sv);
             if (gcons.on && gcons.output && !sampled) {
               std::string we;
-              if (!ofio::write_tiff_f32(im["output"].asString() + "_" + key + "_fb.tiff", fs.data() + px * b, W, h,
+              if (!ofio::write_tiff_f32(im["output"].asString() + "_" + key + (gcons.radius ? "_zncc.tiff" : "_fb.tiff"), fs.data() + px * b, W, h,
                                         4 * (size_t)W, we)) {
                 e = we, ok = false;
                 dc.faulted = false;
@@ -1954,7 +2034,7 @@ static int from_file(Value &args, bool plan_only) {
               if (gcons.on)   // solves[b][kk]: this key's record, for the candidates and the kept
                 random_points(dbg_fx[kk].data() + px * b, dbg_fy[kk].data() + px * b, W, h, items[b].im,
                               args, r, r, mask, false, dbg_fs[kk].data() + px * b, &gcons,
-                              &solves[b][kk]["consistency"]);
+                              &solves[b][kk][check_key(gcons)]);
               else
                 random_points(dbg_fx[kk].data() + px * b, dbg_fy[kk].data() + px * b, W, h,
                               items[b].im, args, r, r, mask, false);

@@ -30,6 +30,7 @@
 #include "tvl1_stack.hpp"
 #include "tvl1_shift.hpp"
 #include "tvl1_fbcheck.hpp"
+#include "tvl1_score.hpp"
 
 // the iteration passes are compiled in tvl1_passes.hip (another instruction scheduler)
 namespace tvl1k {
@@ -3411,6 +3412,135 @@ tvl1_status tvl1_zero_above(tvl1_ctx *c, float *u, float *v, size_t fpitch, cons
                             size_t spitch, int32_t w, int32_t h, float beta, uint64_t *rejected,
                             void *stream) {
   return tvl1_zero_above_batch(c, 1, u, v, fpitch, 0, score, spitch, 0, w, h, beta, rejected, stream);
+}
+
+// ---- Photometric (ZNCC) score of a flow (added under ABI 9; kernels in tvl1_score.hpp,
+// DESIGN 14) ----
+static constexpr int32_t kZnMaxDim = 1 << 19;   // mx * 32 is an exact integer below 2^24
+
+// A plane of each of n pairs (rows of `row` bytes): its span in bytes over the whole batch
+struct ZnPlane {
+  const char *name;
+  const void *p;
+  size_t pitch, stride, row;
+};
+
+static bool zn_overlap(const ZnPlane &a, const ZnPlane &b, int32_t n, int32_t h) {
+  auto span = [&](const ZnPlane &q, uintptr_t &lo, uintptr_t &hi) {
+    lo = reinterpret_cast<uintptr_t>(q.p);
+    hi = lo + (size_t)(n - 1) * q.stride + q.pitch * (size_t)(h - 1) + q.row;
+  };
+  uintptr_t a0, a1, b0, b1;
+  span(a, a0, a1);
+  span(b, b0, b1);
+  return a0 < b1 && b0 < a1;
+}
+
+// What the three calls check about sizes and planes, before anything is launched: nu8 u8 planes
+// first (a pair stride 0 is one shared plane where `shared_ok`), f32 planes after them
+static tvl1_status check_zn(tvl1_ctx *c, int32_t n, int32_t w, int32_t h, const ZnPlane *pl, int np,
+                            int nu8, bool shared_ok) {
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  for (int i = 0; i < np; ++i)
+    if (!pl[i].p) return set_err(c, TVL1_EINVAL, "%s is NULL", pl[i].name);
+  if (n < 1) return set_err(c, TVL1_EINVAL, "n must be >= 1 (got %d)", n);
+  if (w < 1 || h < 1) return set_err(c, TVL1_EINVAL, "bad size %dx%d", w, h);
+  if (w > kZnMaxDim || h > kZnMaxDim)
+    return set_err(c, TVL1_ESIZE, "size %dx%d above 2^19 (the 1/32 px map is no longer exact)", w, h);
+  for (int i = 0; i < np; ++i) {
+    if (i < nu8) {
+      if (pl[i].pitch < (size_t)w) return set_err(c, TVL1_EINVAL, "%s: pitch must be >= w", pl[i].name);
+      if (shared_ok && pl[i].stride == 0) continue;
+    } else {
+      if (pl[i].pitch % 4 || pl[i].pitch < (size_t)w * sizeof(float))
+        return set_err(c, TVL1_EINVAL, "%s: pitch must be a multiple of 4 and >= 4 * w", pl[i].name);
+      if (pl[i].stride % 4)
+        return set_err(c, TVL1_EINVAL, "%s: pair stride must be a multiple of 4", pl[i].name);
+    }
+    if (n > 1 && pl[i].stride < pl[i].pitch * (size_t)(h - 1) + pl[i].row)
+      return set_err(c, TVL1_EINVAL, "%s: pair stride must cover one plane", pl[i].name);
+  }
+  return TVL1_OK;
+}
+
+static void launch_zncc(const ZnccArgs &a, int radius, int m, hipStream_t st) {
+  const int bw = 64 - 2 * radius, bands = (a.w + bw - 1) / bw;   // a band's output columns
+  const dim3 grid((unsigned)((bands + 3) / 4), (unsigned)((a.h + kZnSegRows - 1) / kZnSegRows), (unsigned)m);
+  switch (radius) {
+    case 1: hipLaunchKernelGGL(k_zncc_score<1>, grid, kBlk2, 0, st, a); break;
+    case 2: hipLaunchKernelGGL(k_zncc_score<2>, grid, kBlk2, 0, st, a); break;
+    case 3: hipLaunchKernelGGL(k_zncc_score<3>, grid, kBlk2, 0, st, a); break;
+    default: hipLaunchKernelGGL(k_zncc_score<4>, grid, kBlk2, 0, st, a); break;
+  }
+}
+
+tvl1_status tvl1_zncc_score_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t pitch0,
+                                  size_t stride0, const uint8_t *I1, size_t pitch1, size_t stride1,
+                                  const float *u, const float *v, size_t fpitch, size_t fstride,
+                                  int32_t w, int32_t h, int32_t radius, float *score, size_t spitch,
+                                  size_t sstride, void *stream) {
+  const size_t rb = w > 0 ? (size_t)w : 0;
+  const ZnPlane pl[5] = {{"I0", I0, pitch0, stride0, rb}, {"I1", I1, pitch1, stride1, rb},
+                         {"u", u, fpitch, fstride, 4 * rb}, {"v", v, fpitch, fstride, 4 * rb},
+                         {"score", score, spitch, sstride, 4 * rb}};
+  TVL1_TRY(check_zn(c, n, w, h, pl, 5, 2, true));
+  if (radius < 1 || radius > 4) return set_err(c, TVL1_EINVAL, "radius must be 1..4 (got %d)", radius);
+  for (int i = 0; i < 4; ++i)
+    if (zn_overlap(pl[4], pl[i], n, h)) return set_err(c, TVL1_EINVAL, "score overlaps %s", pl[i].name);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t tok = xprof_begin(c, st);
+  for (int32_t b = 0; b < n; b += kFbChunk) {
+    const int m = std::min(kFbChunk, n - b);
+    ZnccArgs a;
+    a.I0 = I0 + (size_t)b * stride0, a.I1 = I1 + (size_t)b * stride1;
+    a.u = reinterpret_cast<const float *>(reinterpret_cast<const char *>(u) + (size_t)b * fstride);
+    a.v = reinterpret_cast<const float *>(reinterpret_cast<const char *>(v) + (size_t)b * fstride);
+    a.score = reinterpret_cast<float *>(reinterpret_cast<char *>(score) + (size_t)b * sstride);
+    a.p0 = pitch0, a.s0 = stride0, a.p1 = pitch1, a.s1 = stride1;
+    a.fp = fpitch, a.fs = fstride, a.sp = spitch, a.ss = sstride;
+    a.w = w, a.h = h;
+    launch_zncc(a, radius, m, st);
+  }
+  xprof_end(c, st, tok, 14.0 * w * h * n);
+  HIP_TRY(c, hipGetLastError());
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_zncc_score(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
+                            size_t pitch1, const float *u, const float *v, size_t fpitch, int32_t w,
+                            int32_t h, int32_t radius, float *score, size_t spitch, void *stream) {
+  return tvl1_zncc_score_batch(c, 1, I0, pitch0, 0, I1, pitch1, 0, u, v, fpitch, 0, w, h, radius, score,
+                               spitch, 0, stream);
+}
+
+tvl1_status tvl1_warp_by_flow_u8(tvl1_ctx *c, const uint8_t *I1, size_t pitch1, const float *u,
+                                 const float *v, size_t fpitch, int32_t w, int32_t h, uint8_t *dst,
+                                 size_t dpitch, uint8_t *valid, size_t vpitch, void *stream) {
+  const size_t rb = w > 0 ? (size_t)w : 0;
+  // u8 planes first; `valid` only where it is given
+  const ZnPlane pl[5] = {{"I1", I1, pitch1, 0, rb}, {"dst", dst, dpitch, 0, rb},
+                         {"valid", valid ? valid : dst, valid ? vpitch : dpitch, 0, rb},
+                         {"u", u, fpitch, 0, 4 * rb}, {"v", v, fpitch, 0, 4 * rb}};
+  TVL1_TRY(check_zn(c, 1, w, h, pl, 5, 3, false));
+  const int in[3] = {0, 3, 4};
+  for (int o = 1; o < (valid ? 3 : 2); ++o)   // each output against each input
+    for (int i : in)
+      if (zn_overlap(pl[o], pl[i], 1, h))
+        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[o].name, pl[i].name);
+  if (valid && zn_overlap(pl[1], pl[2], 1, h)) return set_err(c, TVL1_EINVAL, "valid overlaps dst");
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t tok = xprof_begin(c, st);
+  WarpFlowArgs a;
+  a.I1 = I1, a.p1 = pitch1, a.u = u, a.v = v, a.fp = fpitch, a.w = w, a.h = h;
+  a.dst = dst, a.dp = dpitch, a.valid = valid, a.vp = vpitch;
+  const dim3 grid((unsigned)((w + 64 * kFbPx - 1) / (64 * kFbPx)), 1u,
+                  (unsigned)std::min((h + 3) / 4, kZnMaxRowGroups));
+  hipLaunchKernelGGL(k_warp_flow_u8, grid, kBlk2, 0, st, a);
+  xprof_end(c, st, tok, (valid ? 11.0 : 10.0) * w * h);
+  HIP_TRY(c, hipGetLastError());
+  return TVL1_OK;
 }
 
 void *tvl1_stream(tvl1_ctx *c) { return c ? (void *)c->own_stream : nullptr; }

@@ -308,6 +308,20 @@ def load_engine() -> C.CDLL:
                                     C.c_size_t, C.c_int32, C.c_int32, C.c_float,
                                     C.POINTER(C.c_uint64), C.c_void_p]
     lib.tvl1_zero_above.restype = C.c_int
+    # photometric (ZNCC) score of a flow (added under ABI 9)
+    lib.tvl1_zncc_score_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_size_t,
+                                          C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_size_t, C.c_size_t, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+    lib.tvl1_zncc_score_batch.restype = C.c_int
+    lib.tvl1_zncc_score.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tvl1_zncc_score.restype = C.c_int
+    lib.tvl1_warp_by_flow_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.tvl1_warp_by_flow_u8.restype = C.c_int
     lib.tvl1_stream.argtypes = [C.c_void_p]
     lib.tvl1_stream.restype = C.c_void_p
     lib.tvl1_set_profiling.argtypes = [C.c_void_p, C.c_int32]
@@ -776,6 +790,70 @@ class Engine:
         torch.cuda.synchronize()
         out = fl.cpu().numpy()
         return out[0], out[1], out[4], rejected
+
+    # ---- photometric (ZNCC) score of a flow (tvl1_zncc_score*, tvl1_warp_by_flow_u8) ----
+    def zncc_score_batch(self, n: int, dI0: int, pitch0: int, stride0: int, dI1: int, pitch1: int,
+                         stride1: int, du: int, dv: int, f_pitch: int, f_stride: int, w: int, h: int,
+                         radius: int, dscore: int, s_pitch: int, s_stride: int, stream: int = 0) -> None:
+        """tvl1_zncc_score_batch on device planes (pitches and pair strides in bytes): 1 - ZNCC of
+        a (2 radius + 1)^2 window of frame0 against frame1 warped back along the flow (du, dv),
+        for n pairs; a frame pair stride 0 is one frame shared by every pair."""
+        self._check(self.lib.tvl1_zncc_score_batch(
+            self.ctx, n, C.c_void_p(dI0 or None), pitch0, stride0, C.c_void_p(dI1 or None), pitch1,
+            stride1, C.c_void_p(du or None), C.c_void_p(dv or None), f_pitch, f_stride, w, h, radius,
+            C.c_void_p(dscore or None), s_pitch, s_stride, C.c_void_p(stream) if stream else None),
+            "tvl1_zncc_score_batch")
+
+    def zncc_score(self, dI0: int, pitch0: int, dI1: int, pitch1: int, du: int, dv: int, f_pitch: int,
+                   w: int, h: int, radius: int, dscore: int, s_pitch: int, stream: int = 0) -> None:
+        """tvl1_zncc_score: one pair."""
+        self._check(self.lib.tvl1_zncc_score(
+            self.ctx, C.c_void_p(dI0 or None), pitch0, C.c_void_p(dI1 or None), pitch1,
+            C.c_void_p(du or None), C.c_void_p(dv or None), f_pitch, w, h, radius,
+            C.c_void_p(dscore or None), s_pitch, C.c_void_p(stream) if stream else None),
+            "tvl1_zncc_score")
+
+    def warp_by_flow_u8(self, dI1: int, pitch1: int, du: int, dv: int, f_pitch: int, w: int, h: int,
+                        ddst: int, d_pitch: int, dvalid: int = 0, v_pitch: int = 0,
+                        stream: int = 0) -> None:
+        """tvl1_warp_by_flow_u8: frame1 warped back along the flow into the u8 plane ddst (0 where
+        the flow leaves the frame) and, with dvalid, the 0/1 plane of px that stay inside."""
+        self._check(self.lib.tvl1_warp_by_flow_u8(
+            self.ctx, C.c_void_p(dI1 or None), pitch1, C.c_void_p(du or None), C.c_void_p(dv or None),
+            f_pitch, w, h, C.c_void_p(ddst or None), d_pitch, C.c_void_p(dvalid or None), v_pitch,
+            C.c_void_p(stream) if stream else None), "tvl1_warp_by_flow_u8")
+
+    def calc_scored(self, I0: np.ndarray, I1: np.ndarray, radius: int = 3, beta: float = 0.25,
+                    init=None):
+        """One forward solve I0 -> I1, its ZNCC score against the two frames, and the flow zeroed
+        where !(score <= beta): calc_consistent's sibling with one solve.  Host u8 arrays of one
+        size in; returns (u, v, score, rejected).  init = (dx, dy): the solve starts from that
+        constant flow (tvl1_calc_batch_const_init)."""
+        import torch
+        I0 = np.array(I0, dtype=np.uint8, order="C")   # copies: torch wants writable arrays
+        I1 = np.array(I1, dtype=np.uint8, order="C")
+        if I1.shape != I0.shape:
+            raise ValueError("I0 and I1 must have the same size")
+        h, w = I0.shape
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d0, d1 = torch.from_numpy(I0).to(dev), torch.from_numpy(I1).to(dev)
+        fl = torch.zeros((3, h, w), dtype=torch.float32, device=dev)   # u, v, score
+        torch.cuda.synchronize()
+        st = self.stream
+        p = [fl[k].data_ptr() for k in range(3)]
+        if init is None:
+            self.calc_device(d0.data_ptr(), w, d1.data_ptr(), w, w, h, p[0], p[1], 4 * w, stream=st,
+                             stats=False)
+        else:
+            seed = np.array([[float(init[0]), float(init[1])]], np.float32)
+            self.calc_batch_device(1, d0.data_ptr(), w, w * h, d1.data_ptr(), w, w * h, w, h,
+                                   p[0], p[1], 4 * w, 4 * w * h, stream=st, init_const=seed)
+        self.zncc_score(d0.data_ptr(), w, d1.data_ptr(), w, p[0], p[1], 4 * w, w, h, radius, p[2],
+                        4 * w, stream=st)
+        rejected = self.zero_above(p[0], p[1], 4 * w, p[2], 4 * w, w, h, beta, stream=st)
+        torch.cuda.synchronize()
+        out = fl.cpu().numpy()
+        return out[0], out[1], out[2], rejected
 
     def close(self):
         if self.ctx:

@@ -496,6 +496,68 @@ tvl1_status tvl1_zero_above(tvl1_ctx *ctx, float *u, float *v, size_t flow_pitch
                             const float *score, size_t score_pitch, int32_t w, int32_t h,
                             float beta, uint64_t *rejected, void *stream);
 
+/* ---- Photometric (ZNCC) score of a flow (added under ABI 9) ----
+ * Given the two u8 frames of a pair and its forward flow (u, v), I1(x + u, y + v) ~ I0(x, y),
+ * frame1 is warped back along the flow and every px is scored by the zero-mean normalised
+ * cross-correlation of a (2 radius + 1)^2 window of frame0 against the warped frame1, in one
+ * pass and without a second solve.  Lower is better: score = 1 - ZNCC, so tvl1_zero_above and
+ * the candidate rule of the forward-backward score apply as they are.
+ *
+ * Step 1, the warped frame J and its validity m.  Per px, every float operation one IEEE f32
+ * rounding, never contracted:
+ *   mx = float(x) + u, my = float(y) + v;
+ *   m = mx >= 0 && mx <= float(w - 1) && my >= 0 && my <= float(h - 1)   (false for NaN);
+ *   where !m nothing is converted and no tap is read; where m:
+ *   ix = rint(mx * 32) (half to even), sx = ix >> 5, fx = ix & 31, x1 = min(sx + 1, w - 1);
+ *   iy, sy, fy, y1 likewise;  s00 = I1[sy][sx], s01 = I1[sy][x1], s10 = I1[y1][sx], s11 = I1[y1][x1];
+ *   J = (s00 (32 - fx)(32 - fy) + s01 fx (32 - fy) + s10 (32 - fx) fy + s11 fx fy + 512) >> 10
+ *   (sx = w - 1 implies fx = 0: the clamped tap carries weight 0).
+ * Step 2, over the window {(x + i, y + j) : |i|, |j| <= radius} cut to the frame and to px with
+ * m, in integers: n = its px, Sa = sum I0, Sb = sum J, Saa = sum I0^2, Sbb = sum J^2, Sab = sum
+ * I0 J;  A = n Sab - Sa Sb, B = n Saa - Sa^2, C = n Sbb - Sb^2 (all below 2^29 for n <= 81).
+ * Step 3: score = +inf where the centre px has !m, or B == 0, or C == 0 (a flat window on either
+ * side is no evidence); otherwise score = float(1.0 - double(A) / sqrt(double(B) * double(C))):
+ * four IEEE f64 operations and one conversion, each rounded once whatever the ctx's fast_math
+ * or profile.  Identical windows score exactly 0, J = 255 - I0 scores exactly 2; a px is
+ * accepted at beta iff score <= beta, that is ZNCC >= 1 - beta.
+ *
+ * All pointers are device pointers, pitches and pair strides in bytes.  The frames may be ROI
+ * views of any pointer and any pitch >= w; the f32 planes of any pointer and pitch that are
+ * multiples of 4.  Pair b's planes lie at base + b * pair stride; a frame pair stride 0 is one
+ * frame shared by every pair, as in tvl1_calc_batch.  Up to 256 pairs share a launch, a larger n
+ * is chunked.  Nothing outside a row's w px or a plane's h rows is read or written.
+ * Asynchronous on `stream`; no solver scratch is touched; with profiling on each call is one
+ * class-2 mark of the ctx's next solve.
+ * TVL1_EINVAL before anything is launched: a null plane, n < 1, w or h < 1, radius outside 1..4,
+ * a frame pitch below w, a flow or score pitch below 4 w or not a multiple of 4, an f32 pair
+ * stride that is not a multiple of 4, a pair stride (other than a frame's 0) that for n > 1 does
+ * not cover one plane, score overlapping any input (judged on each plane's whole span over the
+ * n pairs).  TVL1_ESIZE: w or h above 2^19 (below that mx * 32 is an exact integer under 2^24). */
+tvl1_status tvl1_zncc_score_batch(tvl1_ctx *ctx, int32_t n,
+                                  const uint8_t *I0, size_t pitch0, size_t pair_stride0,
+                                  const uint8_t *I1, size_t pitch1, size_t pair_stride1,
+                                  const float *u, const float *v, size_t flow_pitch, size_t flow_pair_stride,
+                                  int32_t w, int32_t h, int32_t radius,
+                                  float *score, size_t score_pitch, size_t score_pair_stride,
+                                  void *stream);
+
+/* tvl1_zncc_score_batch with n = 1. */
+tvl1_status tvl1_zncc_score(tvl1_ctx *ctx, const uint8_t *I0, size_t pitch0,
+                            const uint8_t *I1, size_t pitch1,
+                            const float *u, const float *v, size_t flow_pitch,
+                            int32_t w, int32_t h, int32_t radius,
+                            float *score, size_t score_pitch, void *stream);
+
+/* Step 1 as a call of its own: dst = J where m and 0 elsewhere (what frame1 looks like warped
+ * onto frame0), and, where `valid` is not NULL, m as a 0/1 u8 plane.  The sample is the score's
+ * own.  TVL1_EINVAL: a null plane (but `valid`), w or h < 1, a u8 pitch below w, a flow pitch
+ * below 4 w or not a multiple of 4, dst or valid overlapping an input or each other.
+ * TVL1_ESIZE as above. */
+tvl1_status tvl1_warp_by_flow_u8(tvl1_ctx *ctx, const uint8_t *I1, size_t pitch1,
+                                 const float *u, const float *v, size_t flow_pitch,
+                                 int32_t w, int32_t h, uint8_t *dst, size_t dst_pitch,
+                                 uint8_t *valid /* or NULL */, size_t valid_pitch, void *stream);
+
 /* The ctx's own non-blocking HIP stream (hipStream_t as void*): callers that keep
  * several pairs in flight on one device give each ctx its own stream this way. */
 void *tvl1_stream(tvl1_ctx *ctx);
