@@ -46,7 +46,7 @@ def shard(n: int, rank: int, world: int, chunk: int = 16) -> List[int]:
 
 def uploads_needed(pairs: Sequence[Pair], order: Sequence[int]) -> int:
     """Slice uploads a worker does when it keeps the last two slices resident
-    (the frame-reuse rule of the CLI, cli/optflow.cpp)."""
+    (the frame-reuse rule of the CLI, cli/pair_worker.cpp)."""
     resident: Tuple[int, int] = (-1, -1)
     n = 0
     for i in order:

@@ -4,7 +4,7 @@ timed around the whole CLI process.
 
     python tools/cli_e2e.py [--slices 17] [--width 6144 --height 4096] [--out DIR]
                             [--format png|tiff|tiff_deflate] [--jobs c2,strips]
-                            [--strip-batch 256,0] [--no-single-thread]
+                            [--strip-batch 256,0] [--no-single-thread] [--bin PATH]
 
 --format tiff writes uncompressed one-strip TIFFs (the strip jobs then read only the ROIs'
 rows of each slice), tiff_deflate deflate TIFFs of 64-row strips (only the strips holding
@@ -25,6 +25,8 @@ sets the rate is the one whose thread-seconds per pair, over the threads doing i
 closest to the wall time per pair.
 --ab-pinned instead runs each job with the decode pool twice with page-locked slices and
 flows and twice pageable (OPTFLOW_PINNED=1/0, alternating).
+--bin PATH runs another build of the CLI (an A/B of two binaries: one call per binary with the
+same --out, whose slices the second call finds and reuses).
 Prints one JSON line per run."""
 import argparse
 import json
@@ -49,6 +51,8 @@ def make_stack(d: Path, Z: int, W: int, H: int, fmt: str = "png"):
     st = DeviceStack(W, H, torch.device("cuda", 0), seed=0x5EED)
     ext = "png" if fmt == "png" else "tif"
     paths = [d / f"s{z:04d}.{ext}" for z in range(Z)]
+    if all(p.exists() for p in paths):   # a stack an earlier call wrote into --out
+        return paths
 
     def save(z):
         a = st_slices[z]
@@ -110,10 +114,14 @@ def main():
     ap.add_argument("--strides", default="1",
                     help="pairs (z, z + s) for each s: a comma list, or A-B for every s in it "
                          "(gen_cross-style long-range pairs; long jobs over one stack)")
+    ap.add_argument("--bin", default=None, help="the optflow binary to run (default: this tree's)")
     ap.add_argument("--ab-env", default=None,
                     help="KEY=VAL[,KEY=VAL]: run each job twice with and twice without these "
                          "environment settings, alternating, on the same stack")
     args = ap.parse_args()
+    if args.bin:
+        global OPTFLOW
+        OPTFLOW = Path(args.bin).resolve()
     d = Path(args.out or tempfile.mkdtemp(prefix="cli_e2e_"))
     d.mkdir(parents=True, exist_ok=True)
     t0 = time.perf_counter()
