@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 #include "../../include/tvl1.h"
 #include "json.hpp"
@@ -123,12 +124,29 @@ inline bool resolve_features(const Value &im, const Value &args) {
 // as in the reference (optflow.cpp:512, never passed to create()).  "initialFlow": "auto" is
 // the same with a constant found per ROI (tvl1_estimate_shift within "initialFlowMaxShift" px,
 // default 32, per image or global); any other value of the key stays inert.
+//
+// "initialFlow": {"chain": [prefix, ...]}, 1 to 64 links, each the "output" value of an earlier
+// pair: the seed is the composition, left to right, of the flows those pairs wrote.
+// For ROI key k a link is read from {prefix}{roi_suffix(k)}_x.tiff and _y.tiff, the links are
+// composed on the device (tvl1_compose_flow, in place) and the ROI is solved by tvl1_calc_init
+// from the result; a chain of one link is a seed read from a file.  The link files must have been
+// written with "output_type": "flow", at this pair's scale and for the same ROI: a map cannot be
+// told from a flow here.  Such pairs are solved one by one, never in a strip batch.
 struct InitFlow {
   bool on = false;
   float dx = 0.f, dy = 0.f;
   bool automatic = false;
   int max_shift = 0;
+  std::vector<std::string> chain;        // the links' prefixes; empty: no chain
+  const char *error = nullptr;           // the key cannot run as written
+  std::vector<uint64_t> outside;         // per composition of a solve: px clamped at the frame edge
+  bool chained() const { return !chain.empty(); }
 };
+constexpr size_t kMaxChainLinks = 64;
+inline const char *const kChainLinks = "initialFlow: \"chain\" must be a list of 1 to 64 output names";
+inline const char *const kChainConsistency =
+    "an initialFlow chain cannot be combined with consistency: the backward solve's seed would be the "
+    "chain's inverse, not its negation";
 inline const char *const kInitFlowFeatures =
     "initialFlow cannot be combined with feature alignment (features, a pair without ROIs, or "
     "frames of different sizes)";
@@ -139,6 +157,18 @@ inline InitFlow initial_flow_of(const Value &im, const Value &args) {
   if (v.isString() && v.asString() == "auto") {
     f.on = f.automatic = true;
     f.max_shift = im.get("initialFlowMaxShift", args.get("initialFlowMaxShift", 32).asInt()).asInt();
+    return f;
+  }
+  if (v.isObject() && v.isMember("chain")) {
+    const Value &c = v["chain"];
+    bool good = c.isArray() && c.size() >= 1 && c.size() <= kMaxChainLinks;
+    for (size_t i = 0; good && i < c.size(); ++i) good = c[i].isString() && !c[i].asString().empty();
+    if (!good) {
+      f.error = kChainLinks;
+      return f;
+    }
+    f.on = true;
+    for (size_t i = 0; i < c.size(); ++i) f.chain.push_back(c[i].asString());
     return f;
   }
   if (!v.isArray() || v.size() != 2) return f;
@@ -280,8 +310,10 @@ struct PairConfig {
   bool sampled() const { return random_points() && !debug; }   // time-seeded draw of npoints px
   // the config names feature alignment beside a seed or a check: nullptr, or why it cannot run
   const char *features_conflict() const {
+    if (init.error) return init.error;
     if (init.on && features) return kInitFlowFeatures;
     if (check_error) return check_error;
+    if (init.chained() && check.on && !check.zncc()) return kChainConsistency;
     if (check.on && features) return check_features_error(check);
     return nullptr;
   }
@@ -343,7 +375,12 @@ inline Value solve_record(const Rect &roi, double seconds, const tvl1_stats &st,
   const size_t nw = std::min((size_t)std::max(0, st.warp_iterations_capacity),
                              (size_t)std::max(0, st.levels) * std::max(1, warps));
   for (size_t k = 0; k < nw; ++k) sv["warp_iterations"][(int)k] = st.warp_iterations[k];
-  if (init.on) {
+  if (init.chained()) {
+    sv["initial_flow_chain"]["links"] = (int64_t)init.chain.size();
+    sv["initial_flow_chain"]["outside"] = Value();
+    for (size_t k = 0; k < init.outside.size(); ++k)
+      sv["initial_flow_chain"]["outside"][(int)k] = (int64_t)init.outside[k];
+  } else if (init.on) {
     sv["initial_flow"][0] = (double)init.dx;
     sv["initial_flow"][1] = (double)init.dy;
   }

@@ -1078,6 +1078,92 @@ bool read_gray8_bands(const std::string &path, double scale,
   }
 }
 
+// ------------------------------------------------------------------ float TIFF read
+// What write_tiff_f32 writes and nothing else: little-endian baseline TIFF, uncompressed, one
+// 32-bit IEEE sample per px, chunky, in one strip or many.  Every offset and count is checked
+// against the file before it is used, and nothing is allocated before the file is known to
+// hold W x H floats.
+bool read_tiff_f32(const std::string &path, int &W_out, int &H_out, HostVec<float> &data, std::string &err) {
+  std::string buf;
+  if (!read_file(path, buf, err, false)) return false;
+  auto bad = [&](const std::string &what) {
+    err = path + ": " + what;
+    return false;
+  };
+  if (buf.size() < 8) return bad("float TIFF: truncated header");
+  const TiffReader t{(const uint8_t *)buf.data(), buf.size(), true};
+  if (buf[0] != 'I' || buf[1] != 'I' || t.u16(2) != 42)
+    return bad("float TIFF: not a little-endian baseline TIFF");
+  const uint32_t ifd = t.u32(4);
+  if ((size_t)ifd + 2 > t.n) return bad("float TIFF: IFD out of range");
+  const uint16_t nent = t.u16(ifd);
+  if ((size_t)ifd + 2 + (size_t)nent * 12 > t.n) return bad("float TIFF: IFD out of range");
+  uint32_t W = 0, H = 0, bps = 1, comp = 1, spp = 1, rps = 0, planar = 1, fmt = 1;
+  std::vector<uint32_t> offs, cnts;
+  // a SHORT or LONG entry's values; false if the type is another or they do not fit in the file
+  auto values = [&](size_t e, std::vector<uint32_t> &v) {
+    const uint16_t type = t.u16(e + 2);
+    const uint32_t cnt = t.u32(e + 4);
+    if (type != 3 && type != 4) return false;
+    const size_t sz = type == 3 ? 2 : 4;
+    const size_t base = (size_t)cnt * sz <= 4 ? e + 8 : t.u32(e + 8);
+    if (base > t.n || (size_t)cnt * sz > t.n - base) return false;
+    v.resize(cnt);
+    for (uint32_t i = 0; i < cnt; ++i) v[i] = sz == 2 ? t.u16(base + (size_t)i * 2) : t.u32(base + (size_t)i * 4);
+    return true;
+  };
+  for (uint16_t i = 0; i < nent; ++i) {
+    const size_t e = ifd + 2 + (size_t)i * 12;
+    const uint16_t tag = t.u16(e);
+    const bool wanted = tag == 256 || tag == 257 || tag == 258 || tag == 259 || tag == 273 || tag == 277 ||
+                        tag == 278 || tag == 279 || tag == 284 || tag == 339;
+    if (!wanted) continue;
+    std::vector<uint32_t> v;
+    if (!values(e, v) || v.empty()) return bad("float TIFF: tag " + std::to_string(tag) + " values out of range");
+    if (tag != 273 && tag != 279 && tag != 258 && tag != 339 && v.size() != 1)
+      return bad("float TIFF: tag " + std::to_string(tag) + " has " + std::to_string(v.size()) + " values");
+    switch (tag) {
+      case 256: W = v[0]; break;
+      case 257: H = v[0]; break;
+      case 258: bps = v[0]; if (v.size() != 1) spp = (uint32_t)v.size(); break;
+      case 259: comp = v[0]; break;
+      case 273: offs = v; break;
+      case 277: spp = v[0]; break;
+      case 278: rps = v[0]; break;
+      case 279: cnts = v; break;
+      case 284: planar = v[0]; break;
+      case 339: fmt = v[0]; if (v.size() != 1) spp = (uint32_t)v.size(); break;
+      default: break;
+    }
+  }
+  if (!W || !H || offs.empty() || offs.size() != cnts.size()) return bad("float TIFF: unsupported layout (need strips)");
+  if (comp != 1) return bad("float TIFF: compression " + std::to_string(comp) + " is not supported (uncompressed only)");
+  if (spp != 1 || planar != 1) return bad("float TIFF: one sample per px only (got " + std::to_string(spp) + ")");
+  if (bps != 32 || fmt != 3)
+    return bad("float TIFF: need 32-bit IEEE float samples (got " + std::to_string(bps) + " bits, sample format " +
+               std::to_string(fmt) + ")");
+  if (W > (1u << 24) || H > (1u << 24) || (uint64_t)W * H > kMaxPixels)
+    return bad("float TIFF: image too large (" + std::to_string(W) + "x" + std::to_string(H) + ")");
+  const size_t rowbytes = (size_t)W * 4;
+  if ((uint64_t)rowbytes * H > t.n) return bad("float TIFF: the file is shorter than its " + std::to_string(W) + "x" +
+                                               std::to_string(H) + " px");
+  if (!rps || rps > H) rps = H;
+  const size_t nstrips = ((size_t)H + rps - 1) / rps;
+  if (offs.size() != nstrips)
+    return bad("float TIFF: " + std::to_string(offs.size()) + " strips for " + std::to_string(nstrips));
+  data.resize((size_t)W * H);
+  for (size_t s = 0; s < nstrips; ++s) {
+    const size_t rows = std::min<size_t>(rps, (size_t)H - s * rps);
+    if ((size_t)cnts[s] != rows * rowbytes) return bad("float TIFF: strip " + std::to_string(s) + " has the wrong size");
+    if ((size_t)offs[s] > t.n || (size_t)cnts[s] > t.n - offs[s])
+      return bad("float TIFF: strip " + std::to_string(s) + " out of range");
+    memcpy((char *)data.data() + s * rps * rowbytes, t.p + offs[s], cnts[s]);
+  }
+  W_out = (int)W;
+  H_out = (int)H;
+  return true;
+}
+
 // ------------------------------------------------------------------ TIFF write
 static bool write_tiff(const std::string &path, const void *data, int W, int H, size_t pitch,
                        int bps, int fmt, std::string &err) {

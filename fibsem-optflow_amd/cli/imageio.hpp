@@ -105,6 +105,13 @@ bool read_gray8_bands(const std::string &path, double scale,
 // Single-channel float32 TIFF (uncompressed, SampleFormat=IEEE float).
 bool write_tiff_f32(const std::string &path, const float *data, int width, int height,
                     size_t pitch_bytes, std::string &err);
+// What write_tiff_f32 writes, read back (a flow file of an earlier job: the links of an
+// "initialFlow" chain): little-endian baseline TIFF, uncompressed, one 32-bit IEEE float sample
+// per px, in one strip or many; data is packed, pitch == width.  Anything else -- compressed,
+// integer or 8/16/64-bit samples, several samples, big-endian, strips or an IFD outside the file,
+// a file shorter than its size says -- is a clean error that names the file.
+bool read_tiff_f32(const std::string &path, int &width, int &height, HostVec<float> &data,
+                   std::string &err);
 // Single-channel 8-bit TIFF (uncompressed).
 bool write_tiff_u8(const std::string &path, const Image8 &img, std::string &err);
 

@@ -43,7 +43,12 @@
 //     too small for a search of 1 px is solved unseeded).  There is no gate on the estimate:
 //     stats_json's "initial_flow_auto" carries sad / count, the summed and counted absolute
 //     differences over the overlap at the estimate, and sad_zero / count_zero, the same at
-//     (0, 0); a drift outside the search range shows as two means that barely differ);
+//     (0, 0); a drift outside the search range shows as two means that barely differ; or
+//     {"chain": [output of an earlier pair, ...]}, 1 to 64 links: each ROI's seed is the
+//     composition, left to right, of the flows those pairs wrote for the same ROI key,
+//     {link}{suffix}_x.tiff / _y.tiff, tvl1_compose_flow, DESIGN 15 -- the files must hold
+//     "output_type": "flow" at this pair's scale, a map cannot be told from a flow; such pairs are
+//     never batched, and not combined with "consistency");
 //     "seededStripBatch" (default false: a seeded pair leaves the strip batch and its ROIs are
 //     solved one by one; true: a pair the *global* "useInitialFlow" / "initialFlow" seeds stays
 //     in its tvl1_calc_batch chunk -- a numeric seed through tvl1_calc_batch_const_init,
@@ -91,6 +96,10 @@ Value plan_entry(const JobState &job, size_t i, const Value &im, const PairConfi
     pl["initialFlow"] = "auto";   // tvl1_estimate_shift, then tvl1_calc_init, per ROI (or,
                                   // strip_batch: tvl1_calc_batch_auto_init per ROI key)
     pl["initialFlowMaxShift"] = cfg.init.max_shift;
+  } else if (cfg.init.chained()) {   // the links' flow files composed (tvl1_compose_flow), then
+                                     // tvl1_calc_init, per ROI; never in a strip batch
+    for (const std::string &link : cfg.init.chain) pl["initialFlow"]["chain"].append(link);
+    pl["initialFlow"]["links"] = (int64_t)cfg.init.chain.size();
   } else if (cfg.init.on) {   // tvl1_calc_init per ROI
     pl["initialFlow"][0] = (double)cfg.init.dx;
     pl["initialFlow"][1] = (double)cfg.init.dy;
@@ -132,9 +141,12 @@ int fail(const std::string &what) {
 // a config that cannot run as written ends the job before any slice is read
 int check_job(Value &images, const Value &args) {
   const size_t n = images.size();
-  for (size_t i = 0; i < n; ++i)
-    if (initial_flow_of(images[i], args).on && resolve_features(images[i], args))
+  for (size_t i = 0; i < n; ++i) {
+    const InitFlow f = initial_flow_of(images[i], args);
+    if (f.error) return fail("pair " + std::to_string(i) + ": " + f.error);
+    if (f.on && resolve_features(images[i], args))
       return fail("pair " + std::to_string(i) + ": " + kInitFlowFeatures);
+  }
   for (size_t i = 0; i < n; ++i) {
     const char *ce = nullptr;
     const FlowCheck ck = check_of(images[i], args, &ce);
@@ -173,7 +185,9 @@ int split_pairs(JobState &job, bool strip_job) {
     static const char *kProd[] = {"p", "q", "pId", "qId", "pGroupId", "qGroupId", "output_name", "output"};
     for (size_t i = 0; i < job.n; ++i) {
       // a seeded pair's ROIs are solved one by one (tvl1_calc_init), or "seededStripBatch"
-      bool ok = job.images[i].isObject() && (seeded_batch || !initial_flow_of(job.images[i], args).on);
+      // (a chained pair always: its seed is a plane per ROI, read from the links' files)
+      const InitFlow seed = initial_flow_of(job.images[i], args);
+      bool ok = job.images[i].isObject() && !seed.chained() && (seeded_batch || !seed.on);
       for (auto &k : job.images[i].memberNames())
         ok = ok && std::find_if(std::begin(kProd), std::end(kProd), [&](const char *x) { return k == x; }) !=
                        std::end(kProd);
@@ -410,6 +424,21 @@ int main(int argc, const char *argv[]) {
         return 1;
       }
       printf("%dx%d %s\n", W, H, partial ? "partial" : "whole");
+      return 0;
+    }
+    if (a == "--decode-flow") {   // tests: a flow file read as a chain's link is, and rewritten
+      if (i + 2 >= argc) {
+        usage();
+        return 2;
+      }
+      int W = 0, H = 0;
+      ofio::HostVec<float> data;
+      std::string err;
+      if (!ofio::read_tiff_f32(argv[i + 1], W, H, data, err) ||
+          !ofio::write_tiff_f32(argv[i + 2], data.data(), W, H, (size_t)W * sizeof(float), err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return 1;
+      }
       return 0;
     }
     if (a == "--decode") {

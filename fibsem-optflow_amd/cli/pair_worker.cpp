@@ -37,8 +37,49 @@ struct RoiViews {
 bool solve_seeded(DeviceCtx &dc, const uint8_t *I0, size_t p0, const uint8_t *I1, size_t p1, const RoiViews &r,
                   const InitFlow &seed, float sign, float *u, float *v, tvl1_stats *st, std::string &err) {
   if (!seed.on) return !dc.failed(tvl1_calc(dc.ctx, I0, p0, I1, p1, r.W, r.H, u, v, r.fp, st, dc.stream), err);
-  if (!fill_seed(dc, u, v, sign * seed.dx, sign * seed.dy, (size_t)r.W * r.H, err)) return false;
+  // a chain's seed is in (u, v) already (load_chain)
+  if (!seed.chained() && !fill_seed(dc, u, v, sign * seed.dx, sign * seed.dy, (size_t)r.W * r.H, err)) return false;
   return !dc.failed(tvl1_calc_init(dc.ctx, I0, p0, I1, p1, r.W, r.H, u, v, r.fp, u, v, r.fp, st, dc.stream), err);
+}
+
+// "initialFlow": {"chain": [...]}: the links' flow files of this ROI key, composed left to right
+// on the device, in place on (dc.du, dc.dv); a link waits in (dc.dub, dc.dvb) while it is composed.
+// A link that is missing, unreadable or of another size fails the pair with its file's name.
+bool load_chain(DeviceCtx &dc, const Value &im, InitFlow &init, const RoiViews &r, std::string &err) {
+  const std::string suffix = im["output_suffix"].asString();
+  const size_t bytes = (size_t)r.W * r.H * sizeof(float);
+  init.outside.clear();
+  for (size_t k = 0; k < init.chain.size(); ++k) {
+    float *dst[2] = {k ? dc.dub.f32() : dc.du.f32(), k ? dc.dvb.f32() : dc.dv.f32()};
+    const char *axis[2] = {"_x.tiff", "_y.tiff"};
+    for (int c = 0; c < 2; ++c) {
+      const std::string path = init.chain[k] + suffix + axis[c];
+      ofio::HostVec<float> plane;
+      int w = 0, h = 0;
+      std::string e;
+      if (!ofio::read_tiff_f32(path, w, h, plane, e)) {
+        err = "initialFlow chain, link " + std::to_string(k) + ": " + e;
+        return false;
+      }
+      if (w != r.W || h != r.H) {
+        err = "initialFlow chain, link " + std::to_string(k) + ": " + path + " is " + std::to_string(w) + "x" +
+              std::to_string(h) + ", the ROI is " + std::to_string(r.W) + "x" + std::to_string(r.H);
+        return false;
+      }
+      // the host plane goes back to its pool below: the copy is waited for
+      if (hipMemcpyAsync(dst[c], plane.data(), bytes, hipMemcpyHostToDevice, dc.stream) != hipSuccess ||
+          hipStreamSynchronize(dc.stream) != hipSuccess)
+        return dc.hip_error("upload of a chain link failed", err);
+    }
+    if (!k) continue;
+    uint64_t outside = 0;
+    if (dc.failed(tvl1_compose_flow(dc.ctx, dc.du.f32(), dc.dv.f32(), r.fp, dst[0], dst[1], r.fp, r.W, r.H,
+                                    dc.du.f32(), dc.dv.f32(), r.fp, &outside, dc.stream),
+                  err, "initialFlow chain: "))
+      return false;
+    init.outside.push_back(outside);
+  }
+  return true;
 }
 
 // random_points without the debug flag (points.hpp's sample_points): only the chosen px's flow
@@ -155,6 +196,9 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
     res.stats["solves"].append(solve_record(Rect{r0.x, r0.y, W, H}, secs_since(t0), st, cfg.tv.warps, init, auto_R,
                                             shift, check, rejected, points));
   };
+  if (init.chained() &&
+      (!dc.reserve_check((size_t)W * H * sizeof(float), err) || !load_chain(dc, im, init, v, err)))
+    return false;
   if (!solve_seeded(dc, v.a, v.pitch0, v.b, v.pitch1, v, init, 1.f, dc.du.f32(), dc.dv.f32(), &st, err)) return false;
   FlowSet fs;
   fs.I0 = v.a, fs.pitch0 = v.pitch0, fs.I1 = v.b, fs.pitch1 = v.pitch1;

@@ -30,6 +30,7 @@
 #include "tvl1_stack.hpp"
 #include "tvl1_shift.hpp"
 #include "tvl1_fbcheck.hpp"
+#include "tvl1_compose.hpp"
 #include "tvl1_score.hpp"
 
 // the iteration passes are compiled in tvl1_passes.hip (another instruction scheduler)
@@ -194,6 +195,8 @@ struct tvl1_ctx {
   size_t seed_bytes = 0;                // constants (then two planes for pairs solved alone)
   char *fb_counts = nullptr;            // tvl1_zero_above_batch's per-pair counters (a block of
   size_t fb_bytes = 0;                  // its own: grown, never shrunk, no solver scratch)
+  char *compose_counts = nullptr;       // tvl1_compose_flow_batch's per-pair counters (likewise)
+  size_t compose_bytes = 0;
   int bnblk = 0;                        // partials per pair
   int check = 0;             // TVL1_CHECK=1: synchronise + check after every launch (diagnostics)
 
@@ -3414,6 +3417,70 @@ tvl1_status tvl1_zero_above(tvl1_ctx *c, float *u, float *v, size_t fpitch, cons
   return tvl1_zero_above_batch(c, 1, u, v, fpitch, 0, score, spitch, 0, w, h, beta, rejected, stream);
 }
 
+// ---- Flow composition (added under ABI 9; kernel in tvl1_compose.hpp) ----
+tvl1_status tvl1_compose_flow_batch(tvl1_ctx *c, int32_t n, const float *ua, const float *va,
+                                    size_t apitch, size_t astride, const float *ub, const float *vb,
+                                    size_t bpitch, size_t bstride, int32_t w, int32_t h, float *uc,
+                                    float *vc, size_t cpitch, size_t cstride, uint64_t *outside,
+                                    void *stream) {
+  const FbPlane pl[6] = {{"ua", ua, apitch, astride}, {"va", va, apitch, astride},
+                         {"ub", ub, bpitch, bstride}, {"vb", vb, bpitch, bstride},
+                         {"uc", uc, cpitch, cstride}, {"vc", vc, cpitch, cstride}};
+  TVL1_TRY(check_fb(c, n, w, h, pl, 6));
+  for (int i = 4; i < 6; ++i)
+    for (int k = 2; k < 4; ++k)
+      if (fb_overlap(pl[i], pl[k], n, w, h))
+        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[i].name, pl[k].name);
+  // in place on a: a px reads its own a and nobody else's
+  const bool in_place = uc == ua && vc == va && cpitch == apitch && cstride == astride;
+  if (!in_place)
+    for (int i = 4; i < 6; ++i)
+      for (int k = 0; k < 2; ++k)
+        if (fb_overlap(pl[i], pl[k], n, w, h))
+          return set_err(c, TVL1_EINVAL, "%s overlaps %s without being flow a itself", pl[i].name,
+                         pl[k].name);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long *cnt = nullptr;
+  if (outside) {
+    order_streams(c, st);
+    if (!c->retired.empty()) reap_retired(c, false);
+    const size_t need = kFbChunk * sizeof(unsigned long long);
+    if (need > c->compose_bytes)
+      TVL1_TRY(arena_alloc(c, &c->compose_counts, &c->compose_bytes, need, st));
+    cnt = reinterpret_cast<unsigned long long *>(c->compose_counts);
+  }
+  const size_t tok = xprof_begin(c, st);
+  for (int32_t b = 0; b < n; b += kFbChunk) {
+    const int m = std::min(kFbChunk, n - b);
+    // the next chunk's zero fill is in stream order behind this one's copy
+    if (cnt) HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(unsigned long long), st));
+    ComposeArgs a;
+    a.ua = reinterpret_cast<const float *>(reinterpret_cast<const char *>(ua) + (size_t)b * astride);
+    a.va = reinterpret_cast<const float *>(reinterpret_cast<const char *>(va) + (size_t)b * astride);
+    a.ub = reinterpret_cast<const float *>(reinterpret_cast<const char *>(ub) + (size_t)b * bstride);
+    a.vb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vb) + (size_t)b * bstride);
+    a.uc = reinterpret_cast<float *>(reinterpret_cast<char *>(uc) + (size_t)b * cstride);
+    a.vc = reinterpret_cast<float *>(reinterpret_cast<char *>(vc) + (size_t)b * cstride);
+    a.ap = apitch, a.as = astride, a.bp = bpitch, a.bs = bstride, a.cp = cpitch, a.cs = cstride;
+    a.w = w, a.h = h, a.count = cnt;
+    hipLaunchKernelGGL(k_compose_flow, fb_grid(w, h, m), kBlk2, 0, st, a);
+    if (cnt)
+      HIP_TRY(c, hipMemcpyAsync(outside + b, cnt, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  }
+  xprof_end(c, st, tok, 24.0 * w * h * n);
+  HIP_TRY(c, hipGetLastError());
+  if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_compose_flow(tvl1_ctx *c, const float *ua, const float *va, size_t apitch,
+                              const float *ub, const float *vb, size_t bpitch, int32_t w, int32_t h,
+                              float *uc, float *vc, size_t cpitch, uint64_t *outside, void *stream) {
+  return tvl1_compose_flow_batch(c, 1, ua, va, apitch, 0, ub, vb, bpitch, 0, w, h, uc, vc, cpitch, 0,
+                                 outside, stream);
+}
+
 // ---- Photometric (ZNCC) score of a flow (added under ABI 9; kernels in tvl1_score.hpp,
 // DESIGN 14) ----
 static constexpr int32_t kZnMaxDim = 1 << 19;   // mx * 32 is an exact integer below 2^24
@@ -3571,6 +3638,7 @@ void tvl1_destroy(tvl1_ctx *c) {
   if (c->shift_scratch) (void)hipFree(c->shift_scratch);
   if (c->seed_scratch) (void)hipFree(c->seed_scratch);
   if (c->fb_counts) (void)hipFree(c->fb_counts);
+  if (c->compose_counts) (void)hipFree(c->compose_counts);
   for (auto &r : c->retired) free_retired(r);
   if (c->align_pat) (void)hipFree(c->align_pat);
   if (c->pinned) (void)hipHostFree(c->pinned);

@@ -322,6 +322,16 @@ def load_engine() -> C.CDLL:
                                          C.c_size_t, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
                                          C.c_void_p, C.c_size_t, C.c_void_p]
     lib.tvl1_warp_by_flow_u8.restype = C.c_int
+    # flow composition (added under ABI 9)
+    lib.tvl1_compose_flow_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.tvl1_compose_flow_batch.restype = C.c_int
+    lib.tvl1_compose_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.tvl1_compose_flow.restype = C.c_int
     lib.tvl1_stream.argtypes = [C.c_void_p]
     lib.tvl1_stream.restype = C.c_void_p
     lib.tvl1_set_profiling.argtypes = [C.c_void_p, C.c_int32]
@@ -854,6 +864,70 @@ class Engine:
         torch.cuda.synchronize()
         out = fl.cpu().numpy()
         return out[0], out[1], out[2], rejected
+
+    # ---- flow composition (tvl1_compose_flow*): c(x) = a(x) + b(x + a(x)) ----
+    def compose_flow_batch(self, n: int, dua: int, dva: int, a_pitch: int, a_stride: int, dub: int,
+                           dvb: int, b_pitch: int, b_stride: int, w: int, h: int, duc: int, dvc: int,
+                           c_pitch: int, c_stride: int, stream: int = 0, count: bool = True):
+        """tvl1_compose_flow_batch on device f32 planes (pitches and pair strides in bytes): the
+        flows A -> C of n pairs from their flows a: A -> B and b: B -> C.  c may be a exactly (in
+        place).  Returns the px of each pair that a takes out of the frame (uint64 array of n), or
+        None with count=False (the call then stays asynchronous)."""
+        out = np.zeros(max(1, n), np.uint64) if count else None
+        self._check(self.lib.tvl1_compose_flow_batch(
+            self.ctx, n, C.c_void_p(dua or None), C.c_void_p(dva or None), a_pitch, a_stride,
+            C.c_void_p(dub or None), C.c_void_p(dvb or None), b_pitch, b_stride, w, h,
+            C.c_void_p(duc or None), C.c_void_p(dvc or None), c_pitch, c_stride,
+            out.ctypes.data_as(C.POINTER(C.c_uint64)) if count else None,
+            C.c_void_p(stream) if stream else None), "tvl1_compose_flow_batch")
+        return out[:max(0, n)] if count else None
+
+    def compose_flow(self, dua: int, dva: int, a_pitch: int, dub: int, dvb: int, b_pitch: int, w: int,
+                     h: int, duc: int, dvc: int, c_pitch: int, stream: int = 0, count: bool = True):
+        """tvl1_compose_flow: one pair; returns its px outside the frame (None with count=False)."""
+        out = C.c_uint64(0)
+        self._check(self.lib.tvl1_compose_flow(
+            self.ctx, C.c_void_p(dua or None), C.c_void_p(dva or None), a_pitch,
+            C.c_void_p(dub or None), C.c_void_p(dvb or None), b_pitch, w, h,
+            C.c_void_p(duc or None), C.c_void_p(dvc or None), c_pitch,
+            C.byref(out) if count else None, C.c_void_p(stream) if stream else None),
+            "tvl1_compose_flow")
+        return int(out.value) if count else None
+
+    def compose_chain_host(self, links):
+        """The flow A -> Z of a chain of links A -> B, B -> C, ..., each a (u, v) pair of host
+        float32 planes of one size, composed left to right on the device, in place on the
+        accumulator.  Returns (u, v, outside_counts): the composed flow and, per composition
+        (len(links) - 1 of them), the px the accumulated flow took out of the frame.  The planes
+        travel through torch, as calc_consistent's do: import torch before the first Engine."""
+        import torch
+        links = [(np.asarray(u, np.float32), np.asarray(v, np.float32)) for u, v in links]
+        if not links:
+            raise ValueError("a chain needs at least one link")
+        h, w = links[0][0].shape
+        for u, v in links:
+            if u.shape != (h, w) or v.shape != (h, w):
+                raise ValueError("every link must have the same size")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        fl = torch.from_numpy(np.stack([np.stack(l) for l in links])).to(dev)   # (links, 2, h, w)
+        torch.cuda.synchronize()
+        st = self.stream
+        acc = fl[0]
+        counts = []
+        for k in range(1, len(links)):
+            counts.append(self.compose_flow(acc[0].data_ptr(), acc[1].data_ptr(), 4 * w,
+                                            fl[k, 0].data_ptr(), fl[k, 1].data_ptr(), 4 * w, w, h,
+                                            acc[0].data_ptr(), acc[1].data_ptr(), 4 * w, stream=st))
+        torch.cuda.synchronize()
+        out = acc.cpu().numpy()
+        return out[0], out[1], counts
+
+    def calc_chained_host(self, I0: np.ndarray, I1: np.ndarray, links, warp_iters: bool = True):
+        """compose_chain_host(links) followed by calc_host(I0, I1, init=(u, v)): the pair solved
+        from the chain of the shorter flows that connect its two frames.  Returns calc_host's
+        (u, v, stats, warp_iterations) and the compositions' outside counts."""
+        u0, v0, counts = self.compose_chain_host(links)
+        return self.calc_host(I0, I1, warp_iters=warp_iters, init=(u0, v0)) + (counts,)
 
     def close(self):
         if self.ctx:

@@ -25,6 +25,30 @@ def stack_pairs(Z: int, strides: Sequence[int] = (1,)) -> List[Pair]:
     return out
 
 
+def chain_links(pair: Pair, strides: Sequence[int]) -> List[Pair] | None:
+    """The shorter pairs of a job whose flows, composed left to right (Engine.compose_chain_host,
+    tvl1_compose_flow), seed the solve of `pair` = (z, z + s): a walk from z that takes, at each
+    position, the largest stride of the job smaller than s that does not overshoot z + s.  None
+    when the walk cannot end on z + s (no smaller stride, or none that fits the rest).  With
+    strides (1, 4, 16): (z, z + 4) is four stride-1 links, (z, z + 16) four stride-4 links, and a
+    stride-1 pair has no chain."""
+    z, end = pair
+    s = end - z
+    if s <= 0:
+        raise ValueError("a pair must point forward")
+    if any(t <= 0 for t in strides):
+        raise ValueError("stride must be positive")
+    smaller = sorted({int(t) for t in strides if t < s}, reverse=True)
+    out: List[Pair] = []
+    while z < end:
+        step = next((t for t in smaller if z + t <= end), None)
+        if step is None:
+            return None
+        out.append((z, z + step))
+        z += step
+    return out or None
+
+
 def chunks(n: int, chunk: int) -> List[Tuple[int, int]]:
     """Contiguous [start, stop) chunks covering range(n)."""
     if chunk <= 0:

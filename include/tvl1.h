@@ -558,6 +558,48 @@ tvl1_status tvl1_warp_by_flow_u8(tvl1_ctx *ctx, const uint8_t *I1, size_t pitch1
                                  int32_t w, int32_t h, uint8_t *dst, size_t dst_pitch,
                                  uint8_t *valid /* or NULL */, size_t valid_pitch, void *stream);
 
+/* ---- Flow composition (added under ABI 9) ----
+ * Given the flow a = (ua, va) of a pair A -> B and the flow b = (ub, vb) of B -> C, a px follows
+ * a, reads b where it lands and adds the two: c(x) = a(x) + b(x + a(x)) is the flow A -> C.
+ * Chained over the short links that connect two distant slices, it is a dense, sub-pixel seed for
+ * their solve (tvl1_calc_init).  Per px, every float operation one IEEE f32 rounding in this
+ * order, never contracted, whatever the ctx's fast_math or profile:
+ *   X = float(x) + ua, Y = float(y) + va;
+ *   inside = X >= 0 && X <= float(w - 1) && Y >= 0 && Y <= float(h - 1)   (false for NaN);
+ *   Xc = X >= 0 ? (X <= float(w - 1) ? X : float(w - 1)) : 0   (NaN and -inf give 0, +inf gives
+ *   w - 1), Yc likewise: no tap is ever read outside the plane, whatever the input;
+ *   x0 = int(floorf(Xc)), ax = Xc - float(x0), x1 = min(x0 + 1, w - 1); y0, ay, y1 likewise;
+ *   for P = ub, vb:  t = P[y0][x0] + ax * (P[y0][x1] - P[y0][x0]),
+ *                    b = P[y1][x0] + ax * (P[y1][x1] - P[y1][x0]),  s = t + ay * (b - t);
+ *   uc = ua + ubs, vc = va + vbs.
+ * A NaN or an infinity in a or b propagates into c; it never becomes an address.
+ * outside: NULL, or n HOST values, the number of px of each pair with !inside (clamped to the
+ * frame's edge before b is read); the call then returns after the counts have arrived (it
+ * synchronizes the stream).  The per-pair counters live in a ctx block of their own.
+ *
+ * All planes are device f32, w x h, ROI views allowed: any pointer and any pitch that are
+ * multiples of 4.  Pair b's planes lie at base + b * pair stride (bytes); up to 256 pairs share
+ * a launch, a larger n is chunked.  Asynchronous on `stream` (but for `outside`); no solver
+ * scratch is touched; with profiling on each call is one class-2 mark of the ctx's next solve.
+ * c may be a exactly (the same pointers, pitch and pair stride: a px reads its own a and nobody
+ * else's, which is what a chain accumulates into).
+ * TVL1_EINVAL before anything is launched: a null plane, n < 1, w or h < 1, a pitch below 4 w or
+ * not a multiple of 4, a pair stride that is not a multiple of 4 or (n > 1) does not cover one
+ * plane, uc / vc overlapping ub / vb, uc / vc overlapping ua / va in any way other than c being a
+ * exactly (overlap is judged on each plane's whole span over the n pairs).  TVL1_ESIZE: w or h
+ * above 2^24, where float(x) is no longer exact. */
+tvl1_status tvl1_compose_flow_batch(tvl1_ctx *ctx, int32_t n,
+                                    const float *ua, const float *va, size_t a_pitch, size_t a_pair_stride,
+                                    const float *ub, const float *vb, size_t b_pitch, size_t b_pair_stride,
+                                    int32_t w, int32_t h,
+                                    float *uc, float *vc, size_t c_pitch, size_t c_pair_stride,
+                                    uint64_t *outside, void *stream);
+
+/* tvl1_compose_flow_batch with n = 1. */
+tvl1_status tvl1_compose_flow(tvl1_ctx *ctx, const float *ua, const float *va, size_t a_pitch,
+                              const float *ub, const float *vb, size_t b_pitch, int32_t w, int32_t h,
+                              float *uc, float *vc, size_t c_pitch, uint64_t *outside, void *stream);
+
 /* The ctx's own non-blocking HIP stream (hipStream_t as void*): callers that keep
  * several pairs in flight on one device give each ctx its own stream this way. */
 void *tvl1_stream(tvl1_ctx *ctx);
