@@ -17,25 +17,9 @@
 
 #include <cfloat>
 
+#include "tvl1_batch_walk.hpp"   // kBatchMax, BatchMask, BatchSel; the host's walk of a level
+
 namespace tvl1k {
-
-constexpr int kBatchMax = 256;
-
-struct BatchMask {           // one bit per pair of a chunk
-  uint64_t w[kBatchMax / 64];
-  __host__ __device__ int test(int b) const { return (int)((w[b >> 6] >> (b & 63)) & 1u); }
-  __host__ void set(int b) { w[b >> 6] |= 1ull << (b & 63); }
-  __host__ void clear(int b) { w[b >> 6] &= ~(1ull << (b & 63)); }
-  __host__ void flip(int b) { w[b >> 6] ^= 1ull << (b & 63); }
-};
-
-struct BatchSel {            // the pairs a launch works on, passed by value
-  int n;                     // number of entries in idx
-  uint8_t idx[kBatchMax];    // pair indices
-  BatchMask ubit, pbit;      // per pair: current u set / p set (0 or 1)
-  BatchMask cerr, pzero;     // per pair: the pass ends in a residual check / p == 0
-  BatchMask storec;          // kb_warp_iter: per pair, store the warp constants to HBM
-};
 
 __device__ __forceinline__ int bsel_bit(const BatchMask &m, int b) { return m.test(b); }
 

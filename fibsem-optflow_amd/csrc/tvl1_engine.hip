@@ -1794,6 +1794,58 @@ static void batch_output(tvl1_ctx *c, int n, int W, int H, float *u, float *v, s
   hipLaunchKernelGGL(kb_output, grid2(W, H, n), kBlk2, 0, st, bo);
 }
 
+// walk_batch_level's backend (tvl1_batch_walk.hpp): the launches of one level of a chunk
+struct BatchOps {
+  const BatchLevel &bl;
+  tvl1_stats *stats;   // per pair, or null
+
+  // build-only median of u before a warp
+  tvl1_status median(const BatchSel &sel) {
+    tvl1_ctx *c = bl.c;
+    BatchMedian md{};
+    set_batch_u(c, md);
+    md.ps = bl.ps;
+    md.W = bl.lw;
+    md.H = bl.lh;
+    md.P = bl.P;
+    md.ksize = c->prm.median_filtering;
+    md.sel = sel;
+    hipLaunchKernelGGL(kb_median, grid2(bl.lw, bl.lh, 2 * bl.n), kBlk2, 0, bl.st, md);
+    return TVL1_OK;
+  }
+  tvl1_status gather(const BatchSel &sel) {
+    launch_batch_ring(bl, sel);
+    return TVL1_OK;
+  }
+  tvl1_status fused(const BatchSel &sel, int nstore, int *blocks) {
+    return (*blocks = launch_batch_warp_iter(bl, sel, nstore)) < 0 ? TVL1_EHIP : TVL1_OK;
+  }
+  tvl1_status pass(int K, const BatchSel &sel, int *blocks) {
+    return (*blocks = launch_batch_roll(bl, K, sel)) < 0 ? TVL1_EHIP : TVL1_OK;
+  }
+  // the fused pass packs each pair's partials (pair stride = their number); a pass leaves
+  // them at the arena's pair stride
+  tvl1_status reduce(const BatchSel &sel, int blocks, bool fused) {
+    tvl1_ctx *c = bl.c;
+    hipLaunchKernelGGL(kb_reduce, dim3(sel.n), dim3(kBlock), 0, bl.st, c->bpartials,
+                       fused ? (size_t)blocks : (size_t)c->bnblk, blocks, sel, c->pinned_dev + 8);
+    return TVL1_OK;
+  }
+  using Residuals = const double *;
+  tvl1_status sync(Residuals *residuals) {
+    tvl1_ctx *c = bl.c;
+    HIP_TRY(c, hipEventRecord(c->ev_check[0], bl.st));
+    HIP_TRY(c, hipEventSynchronize(c->ev_check[0]));
+    *residuals = c->pinned + 8;
+    return TVL1_OK;
+  }
+  void warp_done(int b, int wp, int iters) {
+    const int i = bl.s * bl.c->prm.warps + wp;
+    if (stats && stats[b].warp_iterations && i < stats[b].warp_iterations_capacity)
+      stats[b].warp_iterations[i] = iters;
+  }
+};
+
 static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size_t pitch0,
                                      size_t stride0, const uint8_t *I1, size_t pitch1,
                                      size_t stride1, const Seed *seed, int W, int H, float *u,
@@ -1809,9 +1861,6 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
   // shared share measured neutral here: 2925 / 2901 against 2919 / 2928 strip solves/s,
   // profiles/r3/ab_batch_fill.txt)
   const SolveCount active(c->device);
-  BatchSel all{};
-  all.n = n;
-  for (int b = 0; b < n; ++b) all.idx[b] = (uint8_t)b;
   if (c->profiling) {   // per-class HIP events of this chunk's launches (shared by its pairs)
     c->ev_used = 0;
     c->marks.clear();
@@ -1821,26 +1870,13 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
   TVL1_TRY(batch_initial_flow(c, n, seed, W, H, st));
   HIP_TRY(c, hipGetLastError());
 
-  BatchMask ubit{}, pbit{};
-  std::vector<int64_t> level_iters((size_t)n * TVL1_MAX_LEVELS, 0), checks(n, 0), regathers(n, 0);
-  std::vector<WarpSched> sch(n);        // each pair's procOneScale state in the current warp
-  std::vector<WarpSched::Next> nx(n);   // ... and its next pass
+  BatchWalkState ws(n);   // every pair's buffer sets in use, and the walker's per-pair scratch
+  BatchWalkCounts ct(n);
+  std::vector<int64_t> level_iters((size_t)n * TVL1_MAX_LEVELS, 0);
   std::vector<int> hw;
-  std::vector<char> act(n);
-  // per pair: its previous warp on this level stopped at the first check, so this warp's
-  // fused pass is predicted to stop there too and its constants are not stored (k_warp_iter's
-  // store_c rule)
-  std::vector<char> stopped_first(n, 0);
-  auto note_warp = [&](int b, int s, int wp, int iters) {   // a pair's iterations of a warp
-    level_iters[(size_t)b * TVL1_MAX_LEVELS + s] += iters;
-    if (stats && stats[b].warp_iterations && s * prm.warps + wp < stats[b].warp_iterations_capacity)
-      stats[b].warp_iterations[s * prm.warps + wp] = iters;
-  };
   for (int s = L - 1; s >= 0; --s) {
     const int lw = g.ws[s], lh = g.hs[s], P = g.ps[s];
     const double scaledEps = prm.epsilon * prm.epsilon * (double)lw * (double)lh;
-    BatchMask pzero{};   // p = 0 at every level start
-    for (int b = 0; b < n; ++b) pzero.set(b);
     BatchLevel bl{};
     bl.c = c;
     bl.st = st;
@@ -1861,166 +1897,51 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
     }
     bl.it = iter_args(prm, lw, lh, P, nullptr);   // (each pair's partials are set on the device)
     bl.it.gamma = 0.0f;                           // the batched kernels are the gamma = 0 ones
+    BatchOps ops{bl, stats};
     // the coarsest level runs on chip when it fits one workgroup's registers and LDS (p is
     // reset at every level anyway)
     const bool small = c->batch_small && s == L - 1 && prm.median_filtering <= 1 &&
                        lw <= 64 * kSmallWaves && lh <= kSmallR && lw * lh <= kSmallPx;
     if (small) {
-      TVL1_TRY(batch_small_level(bl, all, seed != nullptr, scaledEps, hw));
+      TVL1_TRY(batch_small_level(bl, ws.all, seed != nullptr, scaledEps, hw));
       for (int b = 0; b < n; ++b) {
-        for (int wp = 0; wp < prm.warps; ++wp) note_warp(b, s, wp, hw[(size_t)b * prm.warps + wp]);
-        checks[b] += hw[(size_t)n * prm.warps + b];
+        ct.level_iters[b] = 0;
+        for (int wp = 0; wp < prm.warps; ++wp) {
+          ops.warp_done(b, wp, hw[(size_t)b * prm.warps + wp]);
+          ct.level_iters[b] += hw[(size_t)b * prm.warps + wp];
+        }
+        ct.checks[b] += hw[(size_t)n * prm.warps + b];
       }
-    }
-    for (int wp = 0; wp < (small ? 0 : prm.warps); ++wp) {
-      if (prm.median_filtering > 1) {   // build-only median of u before each warp
-        BatchMedian md{};
-        set_batch_u(c, md);
-        md.ps = ps;
-        md.W = lw;
-        md.H = lh;
-        md.P = P;
-        md.ksize = prm.median_filtering;
-        md.sel = all;
-        md.sel.ubit = ubit;
-        hipLaunchKernelGGL(kb_median, grid2(lw, lh, 2 * n), kBlk2, 0, st, md);
-        for (int b = 0; b < n; ++b) ubit.flip(b);
-      }
-      BatchSel cur = all;   // every pair, with its current buffer sets
-      cur.ubit = ubit;
+    } else {
+      BatchWalkLevel wl{};
+      wl.n = n;
+      wl.warps = prm.warps;
+      wl.iterations = prm.iterations;
+      wl.kmax = kTbMax;
+      wl.scaledEps = scaledEps;
+      wl.eps_pos = prm.epsilon > 0;
       // warpBackward fused with the warp's first pass, which is 2 iterations ending in the
       // first check for every pair (procOneScale with epsilon > 0, iterations >= 2)
-      const bool fuse = c->batch_fuse && prm.epsilon > 0 && prm.iterations >= 2;
-      // a pair stores its constants unless its previous warp stopped at the first check
-      auto stores = [&](int b) { return wp == 0 || !stopped_first[b] || !c->batch_store_pred; };
-      if (fuse) {
-        cur.pbit = pbit;
-        cur.pzero = pzero;
-        int nstore = 0;
-        for (int b = 0; b < n; ++b)
-          if (stores(b)) {
-            cur.storec.set(b);
-            ++nstore;
-          }
-        const int waves = launch_batch_warp_iter(bl, cur, nstore);
-        if (waves < 0) return TVL1_EHIP;
-        hipLaunchKernelGGL(kb_reduce, dim3(n), dim3(kBlock), 0, st, c->bpartials, (size_t)waves, waves,
-                           all, c->pinned_dev + 8);
-        HIP_TRY(c, hipEventRecord(c->ev_check[0], st));
-      } else {
-        launch_batch_ring(bl, cur);
-      }
-      int nact = 0;
-      for (int b = 0; b < n; ++b) {
-        sch[b] = WarpSched{};
-        act[b] = prm.iterations > 0;
-        nact += act[b];
-      }
-      if (fuse) {   // the fused first pass: n = 0 (no check), n = 1 (check)
-        HIP_TRY(c, hipEventSynchronize(c->ev_check[0]));
-        nact = 0;
-        BatchSel regather{};   // pairs that continue without stored constants
-        regather.ubit = ubit;  // u^0: the set the fused pass read
-        for (int b = 0; b < n; ++b) {
-          const bool stored = stores(b);
-          sch[b].n = 2;
-          ubit.flip(b);
-          pbit.flip(b);
-          pzero.clear(b);
-          sch[b].read(c->pinned[8 + b]);
-          ++checks[b];
-          act[b] = sch[b].active(scaledEps, prm.iterations);
-          nact += act[b];
-          stopped_first[b] = !act[b];
-          if (act[b] && !stored) regather.idx[regather.n++] = (uint8_t)b;
-        }
-        if (regather.n > 0) {   // a wrong guess: gather the constants (k_warp_ring's body)
-          launch_batch_ring(bl, regather);
-          for (int j = 0; j < regather.n; ++j) ++regathers[regather.idx[j]];
-        }
-      } else {
-        for (int b = 0; b < n; ++b) stopped_first[b] = 0;
-      }
-      while (nact > 0) {
-        // each active pair's pass (the single-pair rule, WarpSched): k iterations up to and
-        // including its next check, at most kTbMax
-        int kmin = kTbMax;
-        for (int b = 0; b < n; ++b) {
-          nx[b] = WarpSched::Next{0, false, 0.0};
-          if (!act[b]) continue;
-          nx[b] = sch[b].next(scaledEps, prm.iterations, kTbMax, prm.epsilon > 0);
-          kmin = std::min(kmin, nx[b].k);
-        }
-        // r4: pairs grouped by their pass length, one launch per group, so every pair runs
-        // its whole pass.  TVL1_BATCH_GROUP=0 keeps r3's lock step: one launch of
-        // the shortest pass any active pair allows, the others split theirs (their schedule
-        // clipped to kmin iterations: no check).
-        if (!c->batch_group)
-          for (int b = 0; b < n; ++b)
-            if (act[b] && nx[b].k > kmin) nx[b] = sch[b].next(scaledEps, prm.iterations, kmin, prm.epsilon > 0);
-        for (int K = 1; K <= kTbMax; ++K) {
-          BatchSel sel{};
-          BatchSel chk{};
-          for (int b = 0; b < n; ++b) {
-            if (!act[b] || nx[b].k != K) continue;
-            sel.idx[sel.n++] = (uint8_t)b;
-            if (nx[b].calc_end) {
-              sel.cerr.set(b);
-              chk.idx[chk.n++] = (uint8_t)b;
-            }
-          }
-          if (sel.n == 0) continue;
-          sel.ubit = ubit;
-          sel.pbit = pbit;
-          sel.pzero = pzero;
-          const int blocks = launch_batch_roll(bl, K, sel);
-          if (blocks < 0) return TVL1_EHIP;
-          if (chk.n > 0)
-            hipLaunchKernelGGL(kb_reduce, dim3(chk.n), dim3(kBlock), 0, st, c->bpartials,
-                               (size_t)c->bnblk, blocks, chk, c->pinned_dev + 8);
-        }
-        bool any_check = false;
-        for (int b = 0; b < n; ++b) {
-          if (!act[b]) continue;
-          sch[b].ran(nx[b]);
-          ubit.flip(b);
-          pbit.flip(b);
-          pzero.clear(b);
-          any_check = any_check || nx[b].calc_end;
-        }
-        if (any_check) {
-          HIP_TRY(c, hipEventRecord(c->ev_check[0], st));
-          HIP_TRY(c, hipEventSynchronize(c->ev_check[0]));
-          for (int b = 0; b < n; ++b) {
-            if (!act[b] || !nx[b].calc_end) continue;
-            sch[b].read(c->pinned[8 + b]);
-            ++checks[b];
-          }
-        }
-        nact = 0;
-        for (int b = 0; b < n; ++b) {
-          if (!act[b]) continue;
-          act[b] = sch[b].active(scaledEps, prm.iterations);
-          nact += act[b];
-        }
-      }
-      for (int b = 0; b < n; ++b) note_warp(b, s, wp, sch[b].n);
+      wl.fuse = c->batch_fuse && prm.epsilon > 0 && prm.iterations >= 2;
+      wl.median = prm.median_filtering > 1;
+      // r4: pairs grouped by their pass length, one launch per group, so every pair runs
+      // its whole pass.  TVL1_BATCH_GROUP=0 keeps r3's lock step
+      wl.group = c->batch_group != 0;
+      wl.store_pred = c->batch_store_pred != 0;
+      TVL1_TRY(walk_batch_level(ops, wl, ws, ct));
     }
+    for (int b = 0; b < n; ++b) level_iters[(size_t)b * TVL1_MAX_LEVELS + s] = ct.level_iters[b];
     HIP_TRY(c, hipGetLastError());
     if (s == 0) break;
-    BatchSel cur = all;
-    cur.ubit = ubit;
-    batch_upsample(bl, cur);
-    for (int b = 0; b < n; ++b) ubit.flip(b);
+    batch_upsample(bl, ws.current());
+    ws.flip_u();
   }
-  BatchSel cur = all;
-  cur.ubit = ubit;
-  batch_output(c, n, W, H, u, v, fpitch, fstride, cur, st);
+  batch_output(c, n, W, H, u, v, fpitch, fstride, ws.current(), st);
   HIP_TRY(c, hipGetLastError());
   if (stats)
     for (int b = 0; b < n; ++b)   // misses: constants not stored, then needed (re-gathered)
-      fill_stats(&stats[b], g, prm.warps, &level_iters[(size_t)b * TVL1_MAX_LEVELS], checks[b],
-                 (int32_t)regathers[b]);
+      fill_stats(&stats[b], g, prm.warps, &level_iters[(size_t)b * TVL1_MAX_LEVELS], ct.checks[b],
+                 (int32_t)ct.regathers[b]);
   // with tvl1_set_profiling: every pair of the chunk reports the chunk's launches (each
   // launch serves all its pairs; bytes are summed over them)
   ClassTotals tot;

@@ -1,8 +1,9 @@
 // tvl1_walk.hpp — the control flow of one pyramid level of a single-pair solve as plain C++17:
-// procOneScale's per-warp state (WarpSched, which the batched solve shares) and walk_level, the
-// warp loop over a small launch interface -- the fused first pass and its store-constants
-// rule, the mid-check pass, and speculation: the launch enqueued behind a check,
-// its own check behind that, and the reconciliation after the read.
+// procOneScale's per-warp state (WarpSched) and walk_level, the warp loop over a small launch
+// interface -- the fused first pass and its store-constants rule, the mid-check pass, and
+// speculation: the launch enqueued behind a check, its own check behind that, and
+// the reconciliation after the read.  (The batched solve's level walker, which keeps one
+// WarpSched per pair and shares nothing else, is tvl1_batch_walk.hpp.)
 //
 // No HIP header, like tvl1_plan.hpp.  Unlike the plan, this loop decides which buffer sets a
 // launch reads, which constants are current and which check the host waits for: a slip here

@@ -1,9 +1,14 @@
 """tvl1_calc_batch (the production strip workload): every pair of a batch must
 get exactly the single-pair result -- bit-identical flow and the same per-warp iteration
 counts as the oracle -- whatever the other pairs of the batch do."""
+import functools
+import json
+from pathlib import Path
+
 import numpy as np
 import pytest
 
+import batch_walk_cases
 from optflow_amd import capi, synth
 from oracle import checker
 
@@ -344,6 +349,46 @@ def test_batch_profiling_classes_and_same_bits(built):
         assert st1[b]["kernel_launches"][0] > 0 and st1[b]["kernel_ms"][0] > 0
         assert st1[b]["kernel_hbm_bytes"][0] > 0 and st1[b]["kernel_bytes"][0] > 0
         assert st1[b]["kernel_ms"] == st1[0]["kernel_ms"]   # one chunk: shared launches
+
+
+# The launch sequence of the batched solve, recorded from the engine before its warp loop moved
+# into walk_batch_level (csrc/tvl1_batch_walk.hpp): every pair's per-warp iterations, checks and
+# re-gathers (speculation_misses), and the chunk's launches per class (profiling on), for the
+# chunks of tests/batch_walk_cases.py under the knobs that change the loop's path.  The record is
+# data (tests/golden/batch_walk_sequence.json) and is never re-recorded from the code under
+# test: a number that differs is a change of behaviour.
+BATCH_RECORD = json.loads((Path(__file__).resolve().parent / "golden" / "batch_walk_sequence.json").read_text())
+
+
+@functools.lru_cache(maxsize=None)
+def _recorded_chunk(i):
+    """The pairs of a recorded chunk and their oracle solves (shared by the chunk's knob sets)."""
+    ch = batch_walk_cases.CHUNKS[i]
+    I0s, I1s = batch_walk_cases.chunk_pairs(ch)
+    p = capi.make_params(**ch["params"])
+    return p, I0s, I1s, [checker.oracle_calc(I0s[b], I1s[b], p) for b in range(len(I0s))]
+
+
+@pytest.mark.parametrize("rec", BATCH_RECORD, ids=lambda r: "%s-%s" % (
+    batch_walk_cases.chunk_id(batch_walk_cases.CHUNKS[r["chunk"]]), r["env"] or "default"))
+def test_batch_launch_sequence_as_recorded(built, monkeypatch, rec):
+    for k in batch_walk_cases.KNOB_NAMES:
+        monkeypatch.delenv(k, raising=False)
+    for kv in filter(None, rec["env"].split(",")):
+        monkeypatch.setenv(*kv.split("="))
+    p, I0s, I1s, ref = _recorded_chunk(rec["chunk"])
+    assert len(rec["pairs"]) == len(I0s)
+    eng = capi.Engine(p)
+    eng.set_profiling(True)
+    u, v, st = run_batch(eng, I0s, I1s)
+    eng.close()
+    for b, (r, (ur, vr, sr, wr)) in enumerate(zip(rec["pairs"], ref)):
+        assert [int(x) for x in st[b]["warp_iters"].ravel()] == r["warp_iterations"], b
+        assert st[b]["checks_total"] == r["checks_total"], b
+        assert st[b]["speculation_misses"] == r["speculation_misses"], b
+        assert st[b]["kernel_launches"] == r["kernel_launches"], b
+        np.testing.assert_array_equal(st[b]["warp_iters"], wr, err_msg=f"pair {b}")
+        assert bits_equal(u[b], ur) and bits_equal(v[b], vr), f"pair {b} not bit-exact"
 
 
 def test_batch_constants_on_demand_regather(built, monkeypatch):

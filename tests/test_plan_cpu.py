@@ -64,8 +64,8 @@ def _ints(line):
 
 
 def test_plan_header_is_plain_cxx():
-    """No HIP header: the planner and the level walker compile with any C++17 compiler."""
-    for name in ("tvl1_plan.hpp", "tvl1_walk.hpp"):
+    """No HIP header: the planner and the level walkers compile with any C++17 compiler."""
+    for name in ("tvl1_plan.hpp", "tvl1_walk.hpp", "tvl1_batch_walk.hpp"):
         text = (CSRC / name).read_text()
         assert "hip/" not in text and "__global__" not in text
 
