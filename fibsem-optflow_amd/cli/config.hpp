@@ -10,6 +10,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -132,6 +133,15 @@ inline bool resolve_features(const Value &im, const Value &args) {
 // from the result; a chain of one link is a seed read from a file.  The link files must have been
 // written with "output_type": "flow", at this pair's scale and for the same ROI: a map cannot be
 // told from a flow here.  Such pairs are solved one by one, never in a strip batch.
+//
+// Beside "chain", in the same object:
+//   "inverse": true (default false): the links are the outputs of the pairs that walk from this
+//     pair's frame1 to its frame0, and the seed is tvl1_invert_flow of their composition;
+//   "inverseIterations" (1..32, default 8) and "inverseTolerance" (px^2, finite, default 0.01):
+//     the inversion's K and the bound its unconverged count is taken at;
+//   "backward": "inverse": allows the pair beside "consistency"; the backward solve is seeded by
+//     the inverse of the forward seed (with "inverse": true that is the composed chain itself, so
+//     no second inversion is computed).
 struct InitFlow {
   bool on = false;
   float dx = 0.f, dy = 0.f;
@@ -139,7 +149,14 @@ struct InitFlow {
   int max_shift = 0;
   std::vector<std::string> chain;        // the links' prefixes; empty: no chain
   const char *error = nullptr;           // the key cannot run as written
+  int error_status = 2;                  // ... and the job's exit status for it (the inverse's keys: 1)
   std::vector<uint64_t> outside;         // per composition of a solve: px clamped at the frame edge
+  bool inverse = false;                  // the seed is the inverse of the composed chain
+  bool backward_inverse = false;         // "backward": "inverse"
+  int inverse_iterations = 8;
+  float inverse_tolerance = 0.01f;
+  bool inverted = false;                 // a solve's inversion ran, with these counts
+  tvl1_invert_counts inverse_counts = {0, 0};
   bool chained() const { return !chain.empty(); }
 };
 constexpr size_t kMaxChainLinks = 64;
@@ -147,6 +164,10 @@ inline const char *const kChainLinks = "initialFlow: \"chain\" must be a list of
 inline const char *const kChainConsistency =
     "an initialFlow chain cannot be combined with consistency: the backward solve's seed would be the "
     "chain's inverse, not its negation";
+inline const char *const kChainInverse = "initialFlow: \"inverse\" must be true or false";
+inline const char *const kChainInverseIterations = "initialFlow: \"inverseIterations\" must be an integer from 1 to 32";
+inline const char *const kChainInverseTolerance = "initialFlow: \"inverseTolerance\" must be a finite number (px^2)";
+inline const char *const kChainBackward = "initialFlow: \"backward\" must be \"inverse\"";
 inline const char *const kInitFlowFeatures =
     "initialFlow cannot be combined with feature alignment (features, a pair without ROIs, or "
     "frames of different sizes)";
@@ -166,6 +187,24 @@ inline InitFlow initial_flow_of(const Value &im, const Value &args) {
     if (!good) {
       f.error = kChainLinks;
       return f;
+    }
+    if (const Value *x = v.find("inverse")) {
+      if (x->type() != Value::Bool) return f.error = kChainInverse, f.error_status = 1, f;
+      f.inverse = x->asBool();
+    }
+    if (const Value *x = v.find("inverseIterations")) {
+      if (x->type() != Value::Int || x->asInt64() < 1 || x->asInt64() > 32)
+        return f.error = kChainInverseIterations, f.error_status = 1, f;
+      f.inverse_iterations = x->asInt();
+    }
+    if (const Value *x = v.find("inverseTolerance")) {
+      if ((x->type() != Value::Int && x->type() != Value::Real) || !std::isfinite(x->asFloat()))
+        return f.error = kChainInverseTolerance, f.error_status = 1, f;
+      f.inverse_tolerance = x->asFloat();
+    }
+    if (const Value *x = v.find("backward")) {
+      if (!x->isString() || x->asString() != "inverse") return f.error = kChainBackward, f.error_status = 1, f;
+      f.backward_inverse = true;
     }
     f.on = true;
     for (size_t i = 0; i < c.size(); ++i) f.chain.push_back(c[i].asString());
@@ -313,7 +352,7 @@ struct PairConfig {
     if (init.error) return init.error;
     if (init.on && features) return kInitFlowFeatures;
     if (check_error) return check_error;
-    if (init.chained() && check.on && !check.zncc()) return kChainConsistency;
+    if (init.chained() && check.on && !check.zncc() && !init.backward_inverse) return kChainConsistency;
     if (check.on && features) return check_features_error(check);
     return nullptr;
   }
@@ -380,6 +419,13 @@ inline Value solve_record(const Rect &roi, double seconds, const tvl1_stats &st,
     sv["initial_flow_chain"]["outside"] = Value();
     for (size_t k = 0; k < init.outside.size(); ++k)
       sv["initial_flow_chain"]["outside"][(int)k] = (int64_t)init.outside[k];
+    if (init.inverted) {
+      Value &iv = sv["initial_flow_chain"]["inverse"];
+      iv["iterations"] = init.inverse_iterations;
+      iv["tolerance"] = (double)init.inverse_tolerance;
+      iv["outside"] = (int64_t)init.inverse_counts.outside;
+      iv["unconverged"] = (int64_t)init.inverse_counts.unconverged;
+    }
   } else if (init.on) {
     sv["initial_flow"][0] = (double)init.dx;
     sv["initial_flow"][1] = (double)init.dy;

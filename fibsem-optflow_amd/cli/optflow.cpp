@@ -48,7 +48,12 @@
 //     composition, left to right, of the flows those pairs wrote for the same ROI key,
 //     {link}{suffix}_x.tiff / _y.tiff, tvl1_compose_flow, DESIGN 15 -- the files must hold
 //     "output_type": "flow" at this pair's scale, a map cannot be told from a flow; such pairs are
-//     never batched, and not combined with "consistency");
+//     never batched, and combined with "consistency" only where the same object carries
+//     "backward": "inverse" (the backward solve is seeded by tvl1_invert_flow of the forward
+//     seed); "inverse": true beside "chain" takes the links of the opposite pair
+//     (they walk from frame1 to frame0) and seeds the solve with the inverse of their
+//     composition, by "inverseIterations" steps (1..32, default 8), counting the px whose
+//     residual stays above "inverseTolerance" (px^2, default 0.01) into stats_json);
 //     "seededStripBatch" (default false: a seeded pair leaves the strip batch and its ROIs are
 //     solved one by one; true: a pair the *global* "useInitialFlow" / "initialFlow" seeds stays
 //     in its tvl1_calc_batch chunk -- a numeric seed through tvl1_calc_batch_const_init,
@@ -100,6 +105,12 @@ Value plan_entry(const JobState &job, size_t i, const Value &im, const PairConfi
                                      // tvl1_calc_init, per ROI; never in a strip batch
     for (const std::string &link : cfg.init.chain) pl["initialFlow"]["chain"].append(link);
     pl["initialFlow"]["links"] = (int64_t)cfg.init.chain.size();
+    if (cfg.init.inverse || cfg.init.backward_inverse) {   // tvl1_invert_flow of the composed chain
+      pl["initialFlow"]["inverse"] = cfg.init.inverse;
+      pl["initialFlow"]["inverseIterations"] = cfg.init.inverse_iterations;
+      pl["initialFlow"]["inverseTolerance"] = (double)cfg.init.inverse_tolerance;
+      if (cfg.init.backward_inverse) pl["initialFlow"]["backward"] = "inverse";
+    }
   } else if (cfg.init.on) {   // tvl1_calc_init per ROI
     pl["initialFlow"][0] = (double)cfg.init.dx;
     pl["initialFlow"][1] = (double)cfg.init.dy;
@@ -133,9 +144,9 @@ Value plan_entry(const JobState &job, size_t i, const Value &im, const PairConfi
 
 namespace {
 
-int fail(const std::string &what) {
+int fail(const std::string &what, int status = 2) {
   fprintf(stderr, "Error: %s\n", what.c_str());
-  return 2;
+  return status;
 }
 
 // a config that cannot run as written ends the job before any slice is read
@@ -143,7 +154,7 @@ int check_job(Value &images, const Value &args) {
   const size_t n = images.size();
   for (size_t i = 0; i < n; ++i) {
     const InitFlow f = initial_flow_of(images[i], args);
-    if (f.error) return fail("pair " + std::to_string(i) + ": " + f.error);
+    if (f.error) return fail("pair " + std::to_string(i) + ": " + f.error, f.error_status);
     if (f.on && resolve_features(images[i], args))
       return fail("pair " + std::to_string(i) + ": " + kInitFlowFeatures);
   }

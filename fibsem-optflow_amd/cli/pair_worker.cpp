@@ -82,6 +82,35 @@ bool load_chain(DeviceCtx &dc, const Value &im, InitFlow &init, const RoiViews &
   return true;
 }
 
+// The chain's inverse (tvl1_invert_flow), where the config asks for one.  The composed
+// chain c is in (dc.du, dc.dv); its inverse g goes to (dc.dub, dc.dvb), nothing runs in place.
+//   "inverse": the forward seed is g: copied over c, or, when the backward solve of a
+//     consistency check is seeded too, exchanged with c through dc.dsc (its seed is c itself);
+//   "backward": "inverse" alone: c stays the forward seed and g waits in (dub, dvb), where the
+//     backward solve runs in place.
+bool invert_chain(DeviceCtx &dc, InitFlow &init, const RoiViews &r, bool seed_backward, std::string &err) {
+  init.inverted = false;
+  if (!init.inverse && !seed_backward) return true;
+  const size_t bytes = (size_t)r.W * r.H * sizeof(float);
+  if (dc.failed(tvl1_invert_flow(dc.ctx, dc.du.f32(), dc.dv.f32(), r.fp, init.inverse_iterations,
+                                 init.inverse_tolerance, dc.dub.f32(), dc.dvb.f32(), r.fp, nullptr, 0, r.W, r.H,
+                                 &init.inverse_counts, dc.stream),
+                err, "initialFlow chain, inverse: "))
+    return false;
+  init.inverted = true;
+  if (!init.inverse) return true;
+  const auto copy = [&](float *dst, const float *src) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, dc.stream) == hipSuccess;
+  };
+  bool ok = true;
+  float *fwd[2] = {dc.du.f32(), dc.dv.f32()}, *bwd[2] = {dc.dub.f32(), dc.dvb.f32()};
+  for (int c = 0; c < 2 && ok; ++c) {
+    if (seed_backward) ok = copy(dc.dsc.f32(), fwd[c]) && copy(fwd[c], bwd[c]) && copy(bwd[c], dc.dsc.f32());
+    else ok = copy(fwd[c], bwd[c]);
+  }
+  return ok || dc.hip_error("copy of the inverted chain failed", err);
+}
+
 // random_points without the debug flag (points.hpp's sample_points): only the chosen px's flow
 // (and a checked pair's score) crosses PCIe (tvl1_gather_flow: one upload, one gather, one
 // download), synchronous.  Debug runs keep the exact shuffle so their output is reproducible.
@@ -197,7 +226,8 @@ bool solve_wrapper(DeviceCtx &dc, const ofio::Image8 &f0, const ofio::Image8 &f1
                                             shift, check, rejected, points));
   };
   if (init.chained() &&
-      (!dc.reserve_check((size_t)W * H * sizeof(float), err) || !load_chain(dc, im, init, v, err)))
+      (!dc.reserve_check((size_t)W * H * sizeof(float), err) || !load_chain(dc, im, init, v, err) ||
+       !invert_chain(dc, init, v, init.backward_inverse && check.on && !check.zncc(), err)))
     return false;
   if (!solve_seeded(dc, v.a, v.pitch0, v.b, v.pitch1, v, init, 1.f, dc.du.f32(), dc.dv.f32(), &st, err)) return false;
   FlowSet fs;

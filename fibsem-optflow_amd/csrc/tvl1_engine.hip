@@ -31,6 +31,7 @@
 #include "tvl1_shift.hpp"
 #include "tvl1_fbcheck.hpp"
 #include "tvl1_compose.hpp"
+#include "tvl1_invert.hpp"
 #include "tvl1_score.hpp"
 
 // the iteration passes are compiled in tvl1_passes.hip (another instruction scheduler)
@@ -197,6 +198,10 @@ struct tvl1_ctx {
   size_t fb_bytes = 0;                  // its own: grown, never shrunk, no solver scratch)
   char *compose_counts = nullptr;       // tvl1_compose_flow_batch's per-pair counters (likewise)
   size_t compose_bytes = 0;
+  char *invert_counts = nullptr;        // tvl1_invert_flow_batch's per-pair counter records (likewise)
+  size_t invert_bytes = 0;
+  bool invert_window = true;            // TVL1_INVERT_WINDOW: k_invert_flow's LDS-window arm (the default:
+                                        // 1.9-2.1 x the global arm's rate at K = 8); 0: global gathers
   int bnblk = 0;                        // partials per pair
   int check = 0;             // TVL1_CHECK=1: synchronise + check after every launch (diagnostics)
 
@@ -2182,6 +2187,7 @@ tvl1_status tvl1_create(tvl1_ctx **out, int device, const tvl1_params *params) {
   if (const char *m = getenv("TVL1_MID_MIN")) c->mid_min = atof(m);
   if (const char *m = getenv("TVL1_WI_NC")) c->wi_nc = atoi(m) == 1 ? 1 : 2;
   if (const char *m = getenv("TVL1_TB4")) c->tb4 = atoi(m) != 0;
+  if (const char *m = getenv("TVL1_INVERT_WINDOW")) c->invert_window = atoi(m) != 0;
   if (const char *m = getenv("TVL1_STAGES")) c->stages = std::min(std::max(atoi(m), 0), 2);
   if (const char *m = getenv("TVL1_STAGES_FILL")) c->stages_fill = std::max(0, atoi(m));
   if (const char *m = getenv("TVL1_POLL")) c->poll = atoi(m);
@@ -3402,6 +3408,71 @@ tvl1_status tvl1_compose_flow(tvl1_ctx *c, const float *ua, const float *va, siz
                                  outside, stream);
 }
 
+// ---- Flow inversion (added under ABI 9; kernel in tvl1_invert.hpp) ----
+static_assert(sizeof(tvl1_invert_counts) == 2 * sizeof(unsigned long long), "the kernel's record");
+tvl1_status tvl1_invert_flow_batch(tvl1_ctx *c, int32_t n, const float *uf, const float *vf,
+                                   size_t fpitch, size_t fstride, int32_t iterations, float tol,
+                                   float *ug, float *vg, size_t gpitch, size_t gstride, float *resid,
+                                   size_t rpitch, size_t rstride, int32_t w, int32_t h,
+                                   tvl1_invert_counts *counts, void *stream) {
+  const FbPlane pl[5] = {{"uf", uf, fpitch, fstride}, {"vf", vf, fpitch, fstride},
+                         {"ug", ug, gpitch, gstride}, {"vg", vg, gpitch, gstride},
+                         {"resid", resid, rpitch, rstride}};
+  const int np = resid ? 5 : 4;
+  TVL1_TRY(check_fb(c, n, w, h, pl, np));
+  if (iterations < 1 || iterations > kInvMaxIter)
+    return set_err(c, TVL1_EINVAL, "iterations must be 1..%d (got %d)", kInvMaxIter, iterations);
+  if (std::isnan(tol)) return set_err(c, TVL1_EINVAL, "tol is NaN");
+  // a px reads f at other px: nothing runs in place
+  for (int i = 2; i < np; ++i)
+    for (int k = 0; k < i; ++k)
+      if (fb_overlap(pl[i], pl[k], n, w, h))
+        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[i].name, pl[k].name);
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long *cnt = nullptr;
+  if (counts) {
+    order_streams(c, st);
+    if (!c->retired.empty()) reap_retired(c, false);
+    const size_t need = kFbChunk * sizeof(tvl1_invert_counts);
+    if (need > c->invert_bytes) TVL1_TRY(arena_alloc(c, &c->invert_counts, &c->invert_bytes, need, st));
+    cnt = reinterpret_cast<unsigned long long *>(c->invert_counts);
+  }
+  const size_t tok = xprof_begin(c, st);
+  for (int32_t b = 0; b < n; b += kFbChunk) {
+    const int m = std::min(kFbChunk, n - b);
+    // the next chunk's zero fill is in stream order behind this one's copy
+    if (cnt) HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(tvl1_invert_counts), st));
+    InvertArgs a;
+    a.uf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(uf) + (size_t)b * fstride);
+    a.vf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vf) + (size_t)b * fstride);
+    a.ug = reinterpret_cast<float *>(reinterpret_cast<char *>(ug) + (size_t)b * gstride);
+    a.vg = reinterpret_cast<float *>(reinterpret_cast<char *>(vg) + (size_t)b * gstride);
+    a.resid = resid ? reinterpret_cast<float *>(reinterpret_cast<char *>(resid) + (size_t)b * rstride) : nullptr;
+    a.fp = fpitch, a.fs = fstride, a.gp = gpitch, a.gs = gstride, a.rp = rpitch, a.rs = rstride;
+    a.w = w, a.h = h, a.iters = iterations, a.tol = tol, a.count = cnt;
+    if (c->invert_window)
+      hipLaunchKernelGGL(k_invert_flow<true>, fb_grid(w, h, m), kBlk2, 0, st, a);
+    else
+      hipLaunchKernelGGL(k_invert_flow<false>, fb_grid(w, h, m), kBlk2, 0, st, a);
+    if (cnt)
+      HIP_TRY(c, hipMemcpyAsync(counts + b, cnt, (size_t)m * sizeof(tvl1_invert_counts),
+                                hipMemcpyDeviceToHost, st));
+  }
+  xprof_end(c, st, tok, 20.0 * w * h * n);
+  HIP_TRY(c, hipGetLastError());
+  if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
+  return TVL1_OK;
+}
+
+tvl1_status tvl1_invert_flow(tvl1_ctx *c, const float *uf, const float *vf, size_t fpitch,
+                             int32_t iterations, float tol, float *ug, float *vg, size_t gpitch,
+                             float *resid, size_t rpitch, int32_t w, int32_t h,
+                             tvl1_invert_counts *counts, void *stream) {
+  return tvl1_invert_flow_batch(c, 1, uf, vf, fpitch, 0, iterations, tol, ug, vg, gpitch, 0, resid, rpitch,
+                                0, w, h, counts, stream);
+}
+
 // ---- Photometric (ZNCC) score of a flow (added under ABI 9; kernels in tvl1_score.hpp,
 // DESIGN 14) ----
 static constexpr int32_t kZnMaxDim = 1 << 19;   // mx * 32 is an exact integer below 2^24
@@ -3560,6 +3631,7 @@ void tvl1_destroy(tvl1_ctx *c) {
   if (c->seed_scratch) (void)hipFree(c->seed_scratch);
   if (c->fb_counts) (void)hipFree(c->fb_counts);
   if (c->compose_counts) (void)hipFree(c->compose_counts);
+  if (c->invert_counts) (void)hipFree(c->invert_counts);
   for (auto &r : c->retired) free_retired(r);
   if (c->align_pat) (void)hipFree(c->align_pat);
   if (c->pinned) (void)hipHostFree(c->pinned);

@@ -95,6 +95,11 @@ class TVL1Shift(C.Structure):
     ]
 
 
+class InvertCounts(C.Structure):
+    """tvl1_invert_counts (include/tvl1.h): the per-pair record of tvl1_invert_flow."""
+    _fields_ = [("outside", C.c_uint64), ("unconverged", C.c_uint64)]
+
+
 def shift_dict(r: TVL1Shift) -> dict:
     return dict(dx=int(r.dx), dy=int(r.dy), levels=int(r.levels), sad=int(r.sad),
                 count=int(r.count), sad_zero=int(r.sad_zero), count_zero=int(r.count_zero))
@@ -332,6 +337,16 @@ def load_engine() -> C.CDLL:
                                       C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
     lib.tvl1_compose_flow.restype = C.c_int
+    # flow inversion (added under ABI 9)
+    lib.tvl1_invert_flow_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_size_t, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                                           C.c_int32, C.c_int32, C.POINTER(InvertCounts), C.c_void_p]
+    lib.tvl1_invert_flow_batch.restype = C.c_int
+    lib.tvl1_invert_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_int32, C.c_int32, C.POINTER(InvertCounts), C.c_void_p]
+    lib.tvl1_invert_flow.restype = C.c_int
     lib.tvl1_stream.argtypes = [C.c_void_p]
     lib.tvl1_stream.restype = C.c_void_p
     lib.tvl1_set_profiling.argtypes = [C.c_void_p, C.c_int32]
@@ -922,12 +937,72 @@ class Engine:
         out = acc.cpu().numpy()
         return out[0], out[1], counts
 
-    def calc_chained_host(self, I0: np.ndarray, I1: np.ndarray, links, warp_iters: bool = True):
+    def calc_chained_host(self, I0: np.ndarray, I1: np.ndarray, links, warp_iters: bool = True,
+                          inverse: bool = False, inverse_iterations: int = 8,
+                          inverse_tolerance: float = 0.01):
         """compose_chain_host(links) followed by calc_host(I0, I1, init=(u, v)): the pair solved
         from the chain of the shorter flows that connect its two frames.  Returns calc_host's
-        (u, v, stats, warp_iterations) and the compositions' outside counts."""
+        (u, v, stats, warp_iterations) and the compositions' outside counts.  With inverse=True
+        the links are those of the opposite pair (they walk from I1 to I0), the seed is
+        invert_flow_host of their composition, and the inversion's counts are returned last."""
         u0, v0, counts = self.compose_chain_host(links)
-        return self.calc_host(I0, I1, warp_iters=warp_iters, init=(u0, v0)) + (counts,)
+        if not inverse:
+            return self.calc_host(I0, I1, warp_iters=warp_iters, init=(u0, v0)) + (counts,)
+        u0, v0, inv = self.invert_flow_host(u0, v0, inverse_iterations, inverse_tolerance)
+        return self.calc_host(I0, I1, warp_iters=warp_iters, init=(u0, v0)) + (counts, inv)
+
+    # ---- flow inversion (tvl1_invert_flow*): g(y) = -f(y + g(y)) ----
+    def invert_flow_batch(self, n: int, duf: int, dvf: int, f_pitch: int, f_stride: int,
+                          iterations: int, tol: float, dug: int, dvg: int, g_pitch: int, g_stride: int,
+                          dresid: int, r_pitch: int, r_stride: int, w: int, h: int, stream: int = 0,
+                          counts: bool = True):
+        """tvl1_invert_flow_batch on device f32 planes (pitches and pair strides in bytes): the
+        flows B -> A of n pairs from their flows f: A -> B, by `iterations` fixed-point steps;
+        dresid may be 0 (no residual plane).  Returns an (n, 2) uint64 array of each pair's
+        (outside, unconverged) px, or None with counts=False (the call then stays asynchronous)."""
+        out = (InvertCounts * max(1, n))() if counts else None
+        self._check(self.lib.tvl1_invert_flow_batch(
+            self.ctx, n, C.c_void_p(duf or None), C.c_void_p(dvf or None), f_pitch, f_stride,
+            iterations, tol, C.c_void_p(dug or None), C.c_void_p(dvg or None), g_pitch, g_stride,
+            C.c_void_p(dresid or None), r_pitch, r_stride, w, h, out,
+            C.c_void_p(stream) if stream else None), "tvl1_invert_flow_batch")
+        if not counts:
+            return None
+        return np.array([(out[b].outside, out[b].unconverged) for b in range(max(0, n))],
+                        np.uint64).reshape(-1, 2)
+
+    def invert_flow(self, duf: int, dvf: int, f_pitch: int, iterations: int, tol: float, dug: int,
+                    dvg: int, g_pitch: int, dresid: int, r_pitch: int, w: int, h: int, stream: int = 0,
+                    counts: bool = True):
+        """tvl1_invert_flow: one pair; returns {"outside", "unconverged"} (None with
+        counts=False)."""
+        out = InvertCounts()
+        self._check(self.lib.tvl1_invert_flow(
+            self.ctx, C.c_void_p(duf or None), C.c_void_p(dvf or None), f_pitch, iterations, tol,
+            C.c_void_p(dug or None), C.c_void_p(dvg or None), g_pitch, C.c_void_p(dresid or None),
+            r_pitch, w, h, C.byref(out) if counts else None,
+            C.c_void_p(stream) if stream else None), "tvl1_invert_flow")
+        return dict(outside=int(out.outside), unconverged=int(out.unconverged)) if counts else None
+
+    def invert_flow_host(self, u, v, iterations: int = 8, tol: float = 0.01, resid: bool = False):
+        """The flow B -> A of the host float32 flow (u, v) of A -> B.  Returns (ug, vg, counts), or
+        (ug, vg, resid, counts) with resid=True; counts is invert_flow's record.  The planes
+        travel through torch, as compose_chain_host's do: import torch before the first Engine."""
+        import torch
+        u, v = np.asarray(u, np.float32), np.asarray(v, np.float32)
+        if u.ndim != 2 or u.shape != v.shape:
+            raise ValueError("u and v must be two planes of one size")
+        h, w = u.shape
+        dev = torch.device("cuda", torch.cuda.current_device())
+        f = torch.from_numpy(np.stack([u, v])).to(dev)
+        g = torch.empty((3 if resid else 2, h, w), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        counts = self.invert_flow(f[0].data_ptr(), f[1].data_ptr(), 4 * w, iterations, tol,
+                                  g[0].data_ptr(), g[1].data_ptr(), 4 * w,
+                                  g[2].data_ptr() if resid else 0, 4 * w, w, h, stream=self.stream)
+        torch.cuda.synchronize()
+        out = g.cpu().numpy()
+        return tuple(out) + (counts,)
 
     def close(self):
         if self.ctx:

@@ -600,6 +600,63 @@ tvl1_status tvl1_compose_flow(tvl1_ctx *ctx, const float *ua, const float *va, s
                               const float *ub, const float *vb, size_t b_pitch, int32_t w, int32_t h,
                               float *uc, float *vc, size_t c_pitch, uint64_t *outside, void *stream);
 
+/* ---- Flow inversion (added under ABI 9) ----
+ * Given the flow f = (uf, vf) of a pair A -> B, the flow g = (ug, vg) of B -> A on B's grid: the
+ * fixed point of g(y) = -f(y + g(y)), started at -f(y) and iterated `iterations` (K) times.  It
+ * seeds a solve in the opposite direction to the flows that exist (a reverse pair, or the
+ * backward solve of a consistency check) where the negation -f is wrong by about |grad f| |f|.
+ * Per px (x, y), every float operation one IEEE f32 rounding in this order, never contracted,
+ * whatever the ctx's fast_math or profile:
+ *   g_0 = (-uf[y][x], -vf[y][x]);
+ *   for k = 0 .. K - 1:
+ *     X = float(x) + ug_k, Y = float(y) + vg_k;
+ *     Xc = X >= 0 ? (X <= float(w - 1) ? X : float(w - 1)) : 0   (NaN and -inf give 0, +inf gives
+ *     w - 1), Yc likewise: no tap is ever read outside the plane, whatever the input;
+ *     x0 = int(floorf(Xc)), ax = Xc - float(x0), x1 = min(x0 + 1, w - 1); y0, ay, y1 likewise;
+ *     for P = uf, vf:  t = P[y0][x0] + ax * (P[y0][x1] - P[y0][x0]),
+ *                      b = P[y1][x0] + ax * (P[y1][x1] - P[y1][x0]),  s = t + ay * (b - t);
+ *     g_{k+1} = (-us, -vs);
+ *   one more sample (us, vs) at g_K in the same way, with
+ *     inside = X >= 0 && X <= float(w - 1) && Y >= 0 && Y <= float(h - 1)   (false for NaN);
+ *     ex = ug_K + us, ey = vg_K + vs, resid = ex * ex + ey * ey;
+ *   ug = ug_K, vg = vg_K.
+ * A NaN or an infinity in f propagates into g; it never becomes an address.
+ * resid: NULL, or a score-shaped plane (px^2; tvl1_zero_above and tvl1_gather_flow apply to it
+ * as they are) of how far g is from a fixed point: where f folds, the iteration does not converge.
+ * counts: NULL, or n HOST records: outside, the px of each pair with !inside at the last landing;
+ * unconverged, the px with !(resid <= tol) (NaN counts).  The call then returns after the counts
+ * have arrived (it synchronizes the stream).  The per-pair counters live in a ctx block of their
+ * own.
+ *
+ * All planes are device f32, w x h, ROI views allowed: any pointer and any pitch that are
+ * multiples of 4.  Pair b's planes lie at base + b * pair stride (bytes); up to 256 pairs share
+ * a launch, a larger n is chunked.  Asynchronous on `stream` (but for `counts`); no solver
+ * scratch is touched; with profiling on each call is one class-2 mark of the ctx's next solve.
+ * Nothing runs in place: a px reads f at other px.
+ * TVL1_EINVAL before anything is launched: a null plane (but resid), n < 1, w or h < 1, a pitch
+ * below 4 w or not a multiple of 4, a pair stride that is not a multiple of 4 or (n > 1) does not
+ * cover one plane, iterations outside 1..32, a NaN tol, ug / vg / resid overlapping uf / vf or
+ * each other (overlap is judged on each plane's whole span over the n pairs).  TVL1_ESIZE: w or
+ * h above 2^24, where float(x) is no longer exact. */
+typedef struct {
+    uint64_t outside, unconverged;
+} tvl1_invert_counts;
+
+tvl1_status tvl1_invert_flow_batch(tvl1_ctx *ctx, int32_t n,
+                                   const float *uf, const float *vf, size_t f_pitch, size_t f_pair_stride,
+                                   int32_t iterations, float tol,
+                                   float *ug, float *vg, size_t g_pitch, size_t g_pair_stride,
+                                   float *resid /* or NULL */, size_t resid_pitch, size_t resid_pair_stride,
+                                   int32_t w, int32_t h,
+                                   tvl1_invert_counts *counts /* HOST, n records, or NULL */, void *stream);
+
+/* tvl1_invert_flow_batch with n = 1. */
+tvl1_status tvl1_invert_flow(tvl1_ctx *ctx, const float *uf, const float *vf, size_t f_pitch,
+                             int32_t iterations, float tol,
+                             float *ug, float *vg, size_t g_pitch,
+                             float *resid /* or NULL */, size_t resid_pitch,
+                             int32_t w, int32_t h, tvl1_invert_counts *counts, void *stream);
+
 /* The ctx's own non-blocking HIP stream (hipStream_t as void*): callers that keep
  * several pairs in flight on one device give each ctx its own stream this way. */
 void *tvl1_stream(tvl1_ctx *ctx);
