@@ -300,9 +300,27 @@ TVL1_PLAIN __global__ void k_resize_hp(const float *__restrict__ s0, const float
   float r;
   if (sw == dw && sh == dh) {
     r = src[(size_t)dy * sp + dx];
-  } else if (area_fast) {
+  } else if (area_fast && dx < sw / 2 && 2 * dy + 2 <= sh) {
     const float *S = src + (size_t)(2 * dy) * sp + 2 * dx;
     r = (S[0] + S[1] + S[sp] + S[sp + 1]) * 0.25f;
+  } else if (area_fast) {
+    // the border of an odd source (a size = 3 mod 4 rounds up, 35 -> 18): the taps that
+    // exist, in row-major order, divided by their number (the oracle's operations)
+    float sum = 0.0f;
+    int count = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int yy = 2 * dy + j;
+      if (yy >= sh) continue;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int xx = 2 * dx + i;
+        if (xx >= sw) continue;
+        sum += src[(size_t)yy * sp + xx];
+        ++count;
+      }
+    }
+    r = count > 0 ? sum / (float)count : 0.0f;
   } else {
     float fy = (float)((dy + 0.5) * scale_y - 0.5);
     const int sy = (int)floorf(fy);

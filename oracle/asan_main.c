@@ -1,5 +1,5 @@
 /* TEST INFRASTRUCTURE: drives the oracle under ASan + UBSan (`make -C oracle asan`,
- * tests/test_host_hardening_cpu.py::test_oracle_under_asan).  Solves small synthetic pairs
+ * tests/test_oracle_cpu.py::test_oracle_under_asan_ubsan).  Solves small synthetic pairs
  * at odd sizes through every code path of the restatement: both profiles, gamma, median,
  * fixed work, a pyramid that bottoms out, 1x1 / 16x16 edge sizes, and the seeded entry in
  * both arithmetics (a pitched seed whose taps leave the frame on every side); the fast branch
@@ -7,7 +7,10 @@
  * unseeded, seeded and from f32 frames, with a failing primitive, and uninstalled again; and the
  * pre-alignment restatement (tvl1_oracle_align.c) at its edges: frames with one candidate
  * px and with none, a pitched view, a level quota sum above nfeatures, train sets of 0, 1
- * and 65 descriptors, singular and far-off warps, and a pair of different sizes. */
+ * and 65 descriptors, singular and far-off warps, and a pair of different sizes; and profile 1
+ * on its own edges (tests/dualtvl1_cases.py): scale_step 0.5 on sizes whose levels round up
+ * (35 -> 18: the 2x area path at the border of an odd source), and frames smaller than the
+ * bicubic remap's 4 x 4 taps and the median's window. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -164,6 +167,72 @@ static int align_paths(void) {
   return fails;
 }
 
+/* profile 1: the exact-2x pyramid on odd levels, with and without gamma and the median, u8
+ * and f32 frames; tiny frames under every median size */
+static int dualtvl1_edges(void) {
+  static const int odd[][2] = {{35, 36}, {36, 35}, {35, 35}, {39, 67}, {70, 70}, {33, 37}};
+  static const int tiny[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 3}, {1, 3}, {3, 1},
+                                {4, 5}, {5, 4}, {1, 64}, {64, 1}, {2, 65}};
+  static const int medians[] = {1, 3, 5};
+  int fails = 0;
+  /* 19 x 67 -> 10 x 34 (too small for a pyramid level): the 2x path alone, into exact buffers */
+  {
+    enum { SW = 19, SH = 67, DW = 10, DH = 34 };
+    float *src = malloc(sizeof(float) * SW * SH), *dst = malloc(sizeof(float) * DW * DH);
+    for (int i = 0; i < SW * SH; ++i) src[i] = 1.0f;
+    orc_resize_hp(src, SW, SH, dst, DW, DH, 2.0, 2.0, 1);
+    for (int i = 0; i < DW * DH; ++i)
+      if (dst[i] != 1.0f) {
+        fprintf(stderr, "2x resize of a constant 19x67: %g at %d\n", dst[i], i);
+        ++fails;
+        break;
+      }
+    free(src);
+    free(dst);
+  }
+  for (size_t si = 0; si < sizeof odd / sizeof odd[0] + sizeof tiny / sizeof tiny[0]; ++si) {
+    const int is_odd = si < sizeof odd / sizeof odd[0];
+    const int *sz = is_odd ? odd[si] : tiny[si - sizeof odd / sizeof odd[0]];
+    const int w = sz[0], h = sz[1];
+    uint8_t *a = malloc((size_t)w * h), *b = malloc((size_t)w * h);
+    float *fa = malloc(sizeof(float) * w * h), *fb = malloc(sizeof(float) * w * h);
+    float *u = malloc(sizeof(float) * w * h), *v = malloc(sizeof(float) * w * h);
+    pair(w, h, 101u + (unsigned)si, a, b);
+    for (int i = 0; i < w * h; ++i) fa[i] = (float)a[i] / 255.0f, fb[i] = (float)b[i] / 255.0f;
+    for (int variant = 0; variant < 4; ++variant) {
+      tvl1_params p = {0.25, 0.15, 0.3, 3, 2, 0.01, 300, 0.5, 0.0, 0, 1, 0, 1, 3, 2};
+      if (is_odd) {
+        if (variant == 1) p.gamma = 0.2;
+        if (variant == 2) p.median_filtering = 5, p.nscales = 4;
+      } else {
+        if (variant == 3) continue;
+        p.median_filtering = medians[variant], p.nscales = 1, p.scale_step = 0.8, p.warps = 3;
+      }
+      int32_t wi[32 * 3];
+      tvl1_stats st;
+      memset(&st, 0, sizeof st);
+      st.warp_iterations = wi;
+      st.warp_iterations_capacity = 32 * 3;
+      const int rc = variant == 3 ? orc_tvl1_calc_f32(&p, fa, sizeof(float) * (size_t)w, fb,
+                                                      sizeof(float) * (size_t)w, w, h, u, v,
+                                                      sizeof(float) * (size_t)w, &st)
+                                  : orc_tvl1_calc(&p, a, (size_t)w, b, (size_t)w, w, h, u, v,
+                                                  sizeof(float) * (size_t)w, &st);
+      if (rc != 0 || (is_odd && st.levels < 2) || st.checks_total != st.iterations_total) {
+        fprintf(stderr, "profile 1 %dx%d variant %d: status %d, %d levels\n", w, h, variant, rc, st.levels);
+        ++fails;
+      }
+    }
+    free(a);
+    free(b);
+    free(fa);
+    free(fb);
+    free(u);
+    free(v);
+  }
+  return fails;
+}
+
 int main(void) {
   static const int sizes[][2] = {{1, 1}, {16, 16}, {17, 16}, {33, 19}, {61, 47}, {97, 40}};
   int fails = 0;
@@ -268,6 +337,7 @@ int main(void) {
     free(v);
   }
   fails += align_paths();
+  fails += dualtvl1_edges();
   printf("oracle asan driver: %d failures\n", fails);
   return fails != 0;
 }

@@ -237,7 +237,8 @@ def oracle_postprocess_affine(u: np.ndarray, v: np.ndarray, I1: np.ndarray, flow
 def oracle_check_trace(I0: np.ndarray, I1: np.ndarray, params: TVL1Params | None = None,
                        residual_mode: int = 0, cap: int = 1 << 16, init=None, approx=None):
     """oracle_calc with every check recorded: returns (u, v, stats, warp_iters, trace) where
-    trace is an (n, 4) array of (level, warp, n, error / scaledEps).  residual_mode 1 sums the
+    trace is an (n, 4) array of (level, warp, n, error / scaledEps) -- for profile 1 one record
+    per inner iteration, the ratio of the two floats its rule compares.  residual_mode 1 sums the
     residual in float, rows reversed (orc_set_residual_mode).  init, approx: oracle_calc's seed and fast-branch primitives."""
     lib = load_oracle()
     buf = np.zeros((cap, 4), np.float64)
@@ -268,3 +269,28 @@ def check_margins(trace: np.ndarray, iterations: int) -> np.ndarray:
         ts = [1.0] + [float(t) for t in range(2, max(2, iterations - int(n)) + 1, 2)]
         out[i] = np.inf if r == 0 else min(abs(r - t) for t in ts) / r
     return out
+
+
+# ---- profile 1's remap, counted (orc_set_remap_census)
+CENSUS_CLASSES = ("interior", "left", "right", "top", "bottom", "outside")
+
+
+def oracle_remap_census(I0: np.ndarray, I1: np.ndarray, params: TVL1Params, cap: int = 1 << 12):
+    """oracle_calc of a profile-1 solve with every orc_remap_cubic call counted: returns (u, v,
+    stats, warp_iters, census) where census is an (n_calls, 6) int64 array of px per call in
+    CENSUS_CLASSES' order -- the interior branch; the partial branch with taps missing on the
+    left, right, top, bottom (a px counts once per side); the fully-outside branch."""
+    lib = load_oracle()
+    buf = np.zeros((cap, 6), np.int64)
+    lib.orc_set_remap_census.restype = None
+    lib.orc_set_remap_census.argtypes = [C.c_void_p, C.c_int]
+    lib.orc_remap_census_count.restype = C.c_int
+    lib.orc_set_remap_census(buf.ctypes.data_as(C.c_void_p), cap)
+    try:
+        u, v, st, wi = oracle_calc(I0, I1, params)
+        n = int(lib.orc_remap_census_count())
+    finally:
+        lib.orc_set_remap_census(None, 0)
+    if n > cap:
+        raise RuntimeError(f"remap census overflow ({n} > {cap})")
+    return u, v, st, wi, buf[:n].copy()

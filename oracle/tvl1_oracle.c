@@ -343,7 +343,7 @@ void orc_set_check_trace(double *buf, int cap_records) {
 
 int orc_check_trace_count(void) { return g_trace_n; }
 
-static void trace_check(int level, int warp, int n, double ratio) {
+void orc_trace_check(int level, int warp, int n, double ratio) {
   if (g_trace && g_trace_n < g_trace_cap) {
     double *r = g_trace + 4 * (size_t)g_trace_n;
     r[0] = level, r[1] = warp, r[2] = n, r[3] = ratio;
@@ -760,7 +760,7 @@ static int calc_in(const tvl1_params *prm, const void *I0, size_t pitch0, const 
           error = e;
           prevError = error;
           ++checks;
-          trace_check(s, wp, n, error / scaledEps);
+          orc_trace_check(s, wp, n, error / scaledEps);
         } else {
           error = DBL_MAX;
           prevError -= scaledEps;

@@ -142,6 +142,16 @@ void orc_postprocess_affine(float *u, float *v, size_t flow_pitch, const uint8_t
 void orc_set_residual_mode(int mode);
 void orc_set_check_trace(double *buf, int cap_records);
 int orc_check_trace_count(void);
+/* one record of that trace; profile 1 adds one per inner iteration (n = the warp's iteration
+ * count after it, ratio = (double)(float) error / (double) scaledEps, the two floats its
+ * stopping rule compares) */
+void orc_trace_check(int level, int warp, int n, double ratio);
+/* profile 1's remap, counted: while a buffer is installed every orc_remap_cubic call appends
+ * one record of 6 counts of px -- the interior branch; the partial branch with taps missing
+ * on the left, on the right, at the top, at the bottom (a px counts once per side it
+ * misses); the fully-outside branch.  NULL turns it off.  Process-global, test only. */
+void orc_set_remap_census(int64_t *buf, int cap_records);
+int orc_remap_census_count(void);
 int orc_num_threads(void);
 void orc_set_num_threads(int n);
 

@@ -12,6 +12,10 @@
  *   - cv::resize INTER_LINEAR on CV_32F: half-pixel source coordinate computed in double
  *     and cast to float, x clamped to the edge columns (fx := 0), y NOT clamped (the two
  *     rows are clamped, the weights kept), separable float weights 1-f, f;
+ *   - the exact-2x INTER_AREA fast path (resizeAreaFast_Invoker) at the border of an odd
+ *     source, which the rounded-up destination size reaches (35 -> 18): destination columns
+ *     dx < sw / 2 of rows with 2 dy + 2 <= sh are ((a + b) + c) + d times 0.25f; every other
+ *     px is the float sum of the taps that exist, in row-major order, divided by their count;
  *   - remap INTER_CUBIC: map x + u rounded to 1/32 px (cvRound), Keys a = -0.75 table
  *     (interpolateCubic), 4x4 taps, BORDER_CONSTANT 0 (taps outside add nothing);
  *   - the residual of every inner iteration, here summed in double and cast to float;
@@ -44,11 +48,30 @@ void orc_resize_hp(const float *src, int sw, int sh, float *dst, int dw, int dh,
     return;
   }
   if (area_fast) {   /* resizeAreaFast, scale 2: ((a + b) + c) + d, times 0.25f */
+    const int full_w = sw / 2;   /* destination columns whose two source columns exist */
 #pragma omp parallel for schedule(static)
     for (int dy = 0; dy < dh; ++dy)
       for (int dx = 0; dx < dw; ++dx) {
-        const float *S = src + IDX(2 * dx, 2 * dy, sw);
-        dst[IDX(dx, dy, dw)] = (S[0] + S[1] + S[sw] + S[sw + 1]) * 0.25f;
+        if (dx < full_w && 2 * dy + 2 <= sh) {
+          const float *S = src + IDX(2 * dx, 2 * dy, sw);
+          dst[IDX(dx, dy, dw)] = (S[0] + S[1] + S[sw] + S[sw + 1]) * 0.25f;
+          continue;
+        }
+        /* the border of an odd source (a size = 3 mod 4 rounds up): the taps that exist, in
+         * row-major order, divided by their number */
+        float sum = 0.0f;
+        int count = 0;
+        for (int j = 0; j < 2; ++j) {
+          const int yy = 2 * dy + j;
+          if (yy >= sh) continue;
+          for (int i = 0; i < 2; ++i) {
+            const int xx = 2 * dx + i;
+            if (xx >= sw) continue;
+            sum += src[IDX(xx, yy, sw)];
+            ++count;
+          }
+        }
+        dst[IDX(dx, dy, dw)] = count > 0 ? sum / (float)count : 0.0f;
       }
     return;
   }
@@ -122,12 +145,26 @@ static inline float remap_px(const float *S, int w, int h, int sx, int sy, const
   return sum;
 }
 
+/* the census of orc_set_remap_census: records of 6 counts per orc_remap_cubic call */
+static int64_t *g_census = NULL;
+static int g_census_cap = 0, g_census_n = 0;
+
+void orc_set_remap_census(int64_t *buf, int cap_records) {
+  g_census = buf;
+  g_census_cap = buf ? cap_records : 0;
+  g_census_n = 0;
+}
+
+int orc_remap_census_count(void) { return g_census_n; }
+
 void orc_remap_cubic(const float *I0, const float *I1, const float *I1x, const float *I1y,
                      const float *u1, const float *u2, int w, int h, float *I1wx,
                      float *I1wy, float *grad, float *rho_c) {
   float tab[32][4];
   cubic_tab(tab);
-#pragma omp parallel for schedule(static)
+  /* remap_px's branches, counted (interior, left, right, top, bottom, outside) */
+  long long n_in = 0, n_l = 0, n_r = 0, n_t = 0, n_b = 0, n_out = 0;
+#pragma omp parallel for schedule(static) reduction(+ : n_in, n_l, n_r, n_t, n_b, n_out)
   for (int y = 0; y < h; ++y)
     for (int x = 0; x < w; ++x) {
       const size_t i = IDX(x, y, w);
@@ -135,6 +172,16 @@ void orc_remap_cubic(const float *I0, const float *I1, const float *I1x, const f
       const float X = (float)x + u1[i], Y = (float)y + u2[i];
       const int ix = round_map(X * 32.f), iy = round_map(Y * 32.f);
       const int sx = sat_short(ix >> 5) - 1, sy = sat_short(iy >> 5) - 1;
+      if ((unsigned)sx < (unsigned)imax(w - 3, 0) && (unsigned)sy < (unsigned)imax(h - 3, 0)) {
+        ++n_in;
+      } else if (sx >= w || sx + 4 <= 0 || sy >= h || sy + 4 <= 0) {
+        ++n_out;
+      } else {
+        n_l += sx < 0;
+        n_r += sx + 4 > w;
+        n_t += sy < 0;
+        n_b += sy + 4 > h;
+      }
       const int fx = ix & 31, fy = iy & 31;
       float wt[16];
       for (int k1 = 0; k1 < 4; ++k1)
@@ -150,6 +197,13 @@ void orc_remap_cubic(const float *I0, const float *I1, const float *I1x, const f
       grad[i] = Ix2 + Iy2;
       rho_c[i] = I1w - wx * u1[i] - wy * u2[i] - I0[i];
     }
+  if (g_census) {
+    if (g_census_n < g_census_cap) {
+      int64_t *r = g_census + 6 * (size_t)g_census_n;
+      r[0] = n_in, r[1] = n_l, r[2] = n_r, r[3] = n_t, r[4] = n_b, r[5] = n_out;
+    }
+    ++g_census_n;
+  }
 }
 
 static inline float divergence(const float *v1, const float *v2, int y, int x, int w) {
@@ -338,6 +392,7 @@ int orc_tvl1_calc_dualtvl1_in(const tvl1_params *prm, const void *I0, size_t pit
           estimate_dual_cpu(U1[s], U2[s], U3[s], p11, p12, p21, p22, p31, p32, lw, lh, taut,
                             gamma_f);
           ++n;
+          orc_trace_check(s, wp, n, (double)error / (double)scaledEps);
         }
       }
       level_iters[s] += n;

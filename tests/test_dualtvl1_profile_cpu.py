@@ -55,6 +55,44 @@ def test_resize_hp_area_fast(oracle):
     out = resize(oracle, r, 10, 8, area_fast=1)
     want = (r[0::2, 0::2] + r[0::2, 1::2] + r[1::2, 0::2] + r[1::2, 1::2]) * np.float32(0.25)
     np.testing.assert_allclose(out, want, rtol=1e-6)
+    # odd sources whose destination rounds up (35 -> 18, 19 -> 10, 67 -> 34): the last column
+    # or row has one source column or row; bit for bit against a float32 restatement
+    for sw, sh in ((35, 36), (36, 35), (35, 35), (19, 67)):
+        dw, dh = int(np.rint(sw / 2)), int(np.rint(sh / 2))
+        assert (dw, dh) == {(35, 36): (18, 18), (36, 35): (18, 18), (35, 35): (18, 18),
+                            (19, 67): (10, 34)}[(sw, sh)]
+        r = (np.random.default_rng(sw * 100 + sh).random((sh, sw)) * 255).astype(np.float32)
+        out = resize(oracle, r, dw, dh, area_fast=1)
+        assert np.array_equal(out.view(np.uint32), area_fast_ref(r, dw, dh).view(np.uint32)), (sw, sh)
+        # the border px are means of the taps that exist, not of what lies behind the source
+        if sw % 2:
+            n2 = 2 * (sh // 2)
+            assert np.array_equal(out[:sh // 2, -1], (r[0:n2:2, -1] + r[1:n2:2, -1]) / np.float32(2))
+        if sw % 2 and sh % 2:
+            assert out[-1, -1] == r[-1, -1]
+
+
+def area_fast_ref(src, dw, dh):
+    """The 2x path in float32: ((a + b) + c) + d times 0.25f where all four taps exist
+    (dx < sw / 2 and 2 dy + 2 <= sh), else the sum of the taps that exist in row-major order,
+    from 0.0f, divided by their count."""
+    sh, sw = src.shape
+    out = np.empty((dh, dw), np.float32)
+    for dy in range(dh):
+        for dx in range(dw):
+            if dx < sw // 2 and 2 * dy + 2 <= sh:
+                a, b = src[2 * dy, 2 * dx], src[2 * dy, 2 * dx + 1]
+                c, d = src[2 * dy + 1, 2 * dx], src[2 * dy + 1, 2 * dx + 1]
+                out[dy, dx] = np.float32(np.float32(np.float32(a + b) + c) + d) * np.float32(0.25)
+                continue
+            s, n = np.float32(0), 0
+            for yy in (2 * dy, 2 * dy + 1):
+                for xx in (2 * dx, 2 * dx + 1):
+                    if yy < sh and xx < sw:
+                        s = np.float32(s + src[yy, xx])
+                        n += 1
+            out[dy, dx] = np.float32(s / np.float32(n))
+    return out
 
 
 def test_remap_zero_flow_is_identity(oracle):
