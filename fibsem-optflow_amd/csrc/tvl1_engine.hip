@@ -26,6 +26,7 @@
 #include "tvl1_kernels.hpp"
 #include "tvl1_batch.hpp"
 #include "tvl1_align_plan.hpp"
+#include "tvl1_planes.hpp"
 #include "tvl1_align.hpp"
 #include "tvl1_stack.hpp"
 #include "tvl1_shift.hpp"
@@ -194,12 +195,10 @@ struct tvl1_ctx {
   size_t shift_bytes = 0;
   char *seed_scratch = nullptr;         // tvl1_calc_batch_const_init / _auto_init: every pair's
   size_t seed_bytes = 0;                // constants (then two planes for pairs solved alone)
-  char *fb_counts = nullptr;            // tvl1_zero_above_batch's per-pair counters (a block of
-  size_t fb_bytes = 0;                  // its own: grown, never shrunk, no solver scratch)
-  char *compose_counts = nullptr;       // tvl1_compose_flow_batch's per-pair counters (likewise)
-  size_t compose_bytes = 0;
-  char *invert_counts = nullptr;        // tvl1_invert_flow_batch's per-pair counter records (likewise)
-  size_t invert_bytes = 0;
+  char *count_scratch = nullptr;        // the counted utility calls' per-pair counters (zero_above, compose,
+  size_t count_bytes = 0;               // invert): one block, no solver scratch, sized once for a chunk of
+                                        // the largest record.  Shared safely: a counted call synchronises
+                                        // its stream before it returns, and a ctx is used from one thread
   bool invert_window = true;            // TVL1_INVERT_WINDOW: k_invert_flow's LDS-window arm (the default:
                                         // 1.9-2.1 x the global arm's rate at K = 8); 0: global gathers
   int bnblk = 0;                        // partials per pair
@@ -3206,47 +3205,56 @@ tvl1_status tvl1_postprocess(tvl1_ctx *c, float *u, float *v, size_t fpitch, con
 
 // ---- Forward-backward consistency score (added under ABI 9; kernels in tvl1_fbcheck.hpp,
 // DESIGN 13) ----
+// The utility calls below (this section and DESIGN 14-16) share their argument rules
+// (tvl1_planes.hpp: each states a plane table and an overlap table), pair_at and run_chunks.
 static constexpr int kFbChunk = 256;              // pairs per launch
-static constexpr int32_t kFbMaxDim = 1 << 24;     // float(x) is exact up to here
 
-// One f32 plane of each of n pairs: its span in bytes over the whole batch
-struct FbPlane {
-  const char *name;
-  const void *p;
-  size_t pitch, stride;
-};
-
-static bool fb_overlap(const FbPlane &a, const FbPlane &b, int32_t n, int32_t w, int32_t h) {
-  auto span = [&](const FbPlane &q, uintptr_t &lo, uintptr_t &hi) {
-    lo = reinterpret_cast<uintptr_t>(q.p);
-    hi = lo + (size_t)(n - 1) * q.stride + q.pitch * (size_t)(h - 1) + (size_t)w * sizeof(float);
-  };
-  uintptr_t a0, a1, b0, b1;
-  span(a, a0, a1);
-  span(b, b0, b1);
-  return a0 < b1 && b0 < a1;
+// A tvl1_planes.hpp verdict into the ctx's error text
+static tvl1_status planes_try(tvl1_ctx *c, tvl1_status s, const std::string &msg) {
+  return s == TVL1_OK ? s : set_err(c, s, "%s", msg.c_str());
 }
 
-// Everything tvl1_fb_score_batch and tvl1_zero_above_batch check about sizes and planes, before
-// anything is launched
-static tvl1_status check_fb(tvl1_ctx *c, int32_t n, int32_t w, int32_t h, const FbPlane *pl, int np) {
-  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
-  for (int i = 0; i < np; ++i)
-    if (!pl[i].p) return set_err(c, TVL1_EINVAL, "%s is NULL", pl[i].name);
-  if (n < 1) return set_err(c, TVL1_EINVAL, "n must be >= 1 (got %d)", n);
-  if (w < 1 || h < 1) return set_err(c, TVL1_EINVAL, "bad size %dx%d", w, h);
-  if (w > kFbMaxDim || h > kFbMaxDim)
-    return set_err(c, TVL1_ESIZE, "size %dx%d above 2^24 (float(x) is no longer exact)", w, h);
-  for (int i = 0; i < np; ++i) {
-    if (pl[i].pitch % 4 || pl[i].pitch < (size_t)w * sizeof(float))
-      return set_err(c, TVL1_EINVAL, "%s: pitch must be a multiple of 4 and >= 4 * w", pl[i].name);
-    if (pl[i].stride % 4)
-      return set_err(c, TVL1_EINVAL, "%s: pair stride must be a multiple of 4", pl[i].name);
-    if (n > 1 && pl[i].stride < pl[i].pitch * (size_t)(h - 1) + (size_t)w * sizeof(float))
-      return set_err(c, TVL1_EINVAL, "%s: pair stride must cover one plane", pl[i].name);
+extern "C++" {
+// The plane of pair b: p advanced by b pair strides (bytes)
+template <class T>
+static inline T *pair_at(T *p, int32_t b, size_t stride) {
+  return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(p) + (size_t)b * stride);
+}
+
+// What every batched utility call does around its launches: n pairs in chunks of kFbChunk on
+// `stream`, as one class-2 mark of `bytes` moved.  launch(first pair, pairs in the chunk, the device
+// counters or null) fills the kernel's Args and launches.  With `counts` (HOST, n records of `rec`
+// bytes) each chunk's counters are zeroed before and copied out after its launch, in the ctx's
+// count scratch, and the call returns once they have arrived.
+template <class Launch>
+static tvl1_status run_chunks(tvl1_ctx *c, void *stream, int32_t n, double bytes, void *counts,
+                              size_t rec, Launch launch) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long *cnt = nullptr;
+  if (counts) {
+    order_streams(c, st);
+    if (!c->retired.empty()) reap_retired(c, false);
+    const size_t need = kFbChunk * sizeof(tvl1_invert_counts);   // the largest record
+    if (need > c->count_bytes) TVL1_TRY(arena_alloc(c, &c->count_scratch, &c->count_bytes, need, st));
+    cnt = reinterpret_cast<unsigned long long *>(c->count_scratch);
   }
+  const size_t tok = xprof_begin(c, st);
+  for (int32_t b = 0; b < n; b += kFbChunk) {
+    const int m = std::min(kFbChunk, n - b);
+    // the next chunk's zero fill is in stream order behind this one's copy
+    if (cnt) HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)m * rec, st));
+    launch(b, m, cnt);
+    if (cnt)
+      HIP_TRY(c, hipMemcpyAsync(pair_at(static_cast<char *>(counts), b, rec), cnt, (size_t)m * rec,
+                                hipMemcpyDeviceToHost, st));
+  }
+  xprof_end(c, st, tok, bytes);
+  HIP_TRY(c, hipGetLastError());
+  if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
   return TVL1_OK;
 }
+}  // extern "C++"
 
 static inline dim3 fb_grid(int w, int h, int n) {
   return dim3((unsigned)((w + 64 * kFbPx - 1) / (64 * kFbPx)), (unsigned)n,
@@ -3257,36 +3265,26 @@ tvl1_status tvl1_fb_score_batch(tvl1_ctx *c, int32_t n, const float *uf, const f
                                 size_t fpitch, size_t fstride, const float *ub, const float *vb,
                                 size_t bpitch, size_t bstride, int32_t w, int32_t h, float alpha,
                                 float *score, size_t spitch, size_t sstride, void *stream) {
-  const FbPlane pl[5] = {{"uf", uf, fpitch, fstride}, {"vf", vf, fpitch, fstride},
-                         {"ub", ub, bpitch, bstride}, {"vb", vb, bpitch, bstride},
-                         {"score", score, spitch, sstride}};
-  TVL1_TRY(check_fb(c, n, w, h, pl, 5));
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  const Plane pl[5] = {{"uf", uf, fpitch, fstride}, {"vf", vf, fpitch, fstride},
+                       {"ub", ub, bpitch, bstride}, {"vb", vb, bpitch, bstride},
+                       {"score", score, spitch, sstride}};
+  // score off every flow plane, the backward flow off the forward
+  static constexpr Overlap ov[8] = {{4, 0}, {4, 1}, {4, 2}, {4, 3}, {2, 0}, {3, 0}, {2, 1}, {3, 1}};
+  const PlaneSet ps = {n, w, h, pl, 5, -1};
+  std::string msg;
+  TVL1_TRY(planes_try(c, check_planes(ps, kFloatXLimit, &msg), msg));
   if (std::isnan(alpha)) return set_err(c, TVL1_EINVAL, "alpha is NaN");
-  for (int i = 0; i < 4; ++i)
-    if (fb_overlap(pl[4], pl[i], n, w, h))
-      return set_err(c, TVL1_EINVAL, "score overlaps %s", pl[i].name);
-  for (int i = 0; i < 2; ++i)
-    for (int k = 2; k < 4; ++k)
-      if (fb_overlap(pl[i], pl[k], n, w, h))
-        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[k].name, pl[i].name);
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t tok = xprof_begin(c, st);
-  for (int32_t b = 0; b < n; b += kFbChunk) {
-    const int m = std::min(kFbChunk, n - b);
+  TVL1_TRY(planes_try(c, check_overlaps(ps, ov, 8, false, &msg), msg));
+  return run_chunks(c, stream, n, 20.0 * w * h * n, nullptr, 0, [&](int32_t b, int m, unsigned long long *) {
     FbScoreArgs a;
-    a.uf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(uf) + (size_t)b * fstride);
-    a.vf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vf) + (size_t)b * fstride);
-    a.ub = reinterpret_cast<const float *>(reinterpret_cast<const char *>(ub) + (size_t)b * bstride);
-    a.vb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vb) + (size_t)b * bstride);
-    a.score = reinterpret_cast<float *>(reinterpret_cast<char *>(score) + (size_t)b * sstride);
+    a.uf = pair_at(uf, b, fstride), a.vf = pair_at(vf, b, fstride);
+    a.ub = pair_at(ub, b, bstride), a.vb = pair_at(vb, b, bstride);
+    a.score = pair_at(score, b, sstride);
     a.fp = fpitch, a.fs = fstride, a.bp = bpitch, a.bs = bstride, a.sp = spitch, a.ss = sstride;
     a.w = w, a.h = h, a.alpha = alpha;
-    hipLaunchKernelGGL(k_fb_score, fb_grid(w, h, m), kBlk2, 0, st, a);
-  }
-  xprof_end(c, st, tok, 20.0 * w * h * n);
-  HIP_TRY(c, hipGetLastError());
-  return TVL1_OK;
+    hipLaunchKernelGGL(k_fb_score, fb_grid(w, h, m), kBlk2, 0, (hipStream_t)stream, a);
+  });
 }
 
 tvl1_status tvl1_fb_score(tvl1_ctx *c, const float *uf, const float *vf, size_t fpitch,
@@ -3300,42 +3298,22 @@ tvl1_status tvl1_zero_above_batch(tvl1_ctx *c, int32_t n, float *u, float *v, si
                                   size_t fstride, const float *score, size_t spitch, size_t sstride,
                                   int32_t w, int32_t h, float beta, uint64_t *rejected,
                                   void *stream) {
-  const FbPlane pl[3] = {{"u", u, fpitch, fstride}, {"v", v, fpitch, fstride},
-                         {"score", score, spitch, sstride}};
-  TVL1_TRY(check_fb(c, n, w, h, pl, 3));
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  const Plane pl[3] = {{"u", u, fpitch, fstride}, {"v", v, fpitch, fstride}, {"score", score, spitch, sstride}};
+  static constexpr Overlap ov[2] = {{2, 0}, {2, 1}};
+  const PlaneSet ps = {n, w, h, pl, 3, -1};
+  std::string msg;
+  TVL1_TRY(planes_try(c, check_planes(ps, kFloatXLimit, &msg), msg));
   if (std::isnan(beta)) return set_err(c, TVL1_EINVAL, "beta is NaN");
-  for (int i = 0; i < 2; ++i)
-    if (fb_overlap(pl[2], pl[i], n, w, h))
-      return set_err(c, TVL1_EINVAL, "score overlaps %s", pl[i].name);
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long *cnt = nullptr;
-  if (rejected) {
-    order_streams(c, st);
-    if (!c->retired.empty()) reap_retired(c, false);
-    const size_t need = kFbChunk * sizeof(unsigned long long);
-    if (need > c->fb_bytes) TVL1_TRY(arena_alloc(c, &c->fb_counts, &c->fb_bytes, need, st));
-    cnt = reinterpret_cast<unsigned long long *>(c->fb_counts);
-  }
-  const size_t tok = xprof_begin(c, st);
-  for (int32_t b = 0; b < n; b += kFbChunk) {
-    const int m = std::min(kFbChunk, n - b);
-    // the next chunk's zero fill is in stream order behind this one's copy
-    if (cnt) HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(unsigned long long), st));
+  TVL1_TRY(planes_try(c, check_overlaps(ps, ov, 2, false, &msg), msg));
+  return run_chunks(c, stream, n, 12.0 * w * h * n, rejected, sizeof(uint64_t),
+                    [&](int32_t b, int m, unsigned long long *cnt) {
     ZeroAboveArgs a;
-    a.u = reinterpret_cast<float *>(reinterpret_cast<char *>(u) + (size_t)b * fstride);
-    a.v = reinterpret_cast<float *>(reinterpret_cast<char *>(v) + (size_t)b * fstride);
-    a.score = reinterpret_cast<const float *>(reinterpret_cast<const char *>(score) + (size_t)b * sstride);
+    a.u = pair_at(u, b, fstride), a.v = pair_at(v, b, fstride), a.score = pair_at(score, b, sstride);
     a.fp = fpitch, a.fs = fstride, a.sp = spitch, a.ss = sstride;
     a.w = w, a.h = h, a.beta = beta, a.count = cnt;
-    hipLaunchKernelGGL(k_zero_above, fb_grid(w, h, m), kBlk2, 0, st, a);
-    if (cnt)
-      HIP_TRY(c, hipMemcpyAsync(rejected + b, cnt, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  }
-  xprof_end(c, st, tok, 12.0 * w * h * n);
-  HIP_TRY(c, hipGetLastError());
-  if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
-  return TVL1_OK;
+    hipLaunchKernelGGL(k_zero_above, fb_grid(w, h, m), kBlk2, 0, (hipStream_t)stream, a);
+  });
 }
 
 tvl1_status tvl1_zero_above(tvl1_ctx *c, float *u, float *v, size_t fpitch, const float *score,
@@ -3350,55 +3328,28 @@ tvl1_status tvl1_compose_flow_batch(tvl1_ctx *c, int32_t n, const float *ua, con
                                     size_t bpitch, size_t bstride, int32_t w, int32_t h, float *uc,
                                     float *vc, size_t cpitch, size_t cstride, uint64_t *outside,
                                     void *stream) {
-  const FbPlane pl[6] = {{"ua", ua, apitch, astride}, {"va", va, apitch, astride},
-                         {"ub", ub, bpitch, bstride}, {"vb", vb, bpitch, bstride},
-                         {"uc", uc, cpitch, cstride}, {"vc", vc, cpitch, cstride}};
-  TVL1_TRY(check_fb(c, n, w, h, pl, 6));
-  for (int i = 4; i < 6; ++i)
-    for (int k = 2; k < 4; ++k)
-      if (fb_overlap(pl[i], pl[k], n, w, h))
-        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[i].name, pl[k].name);
-  // in place on a: a px reads its own a and nobody else's
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  const Plane pl[6] = {{"ua", ua, apitch, astride}, {"va", va, apitch, astride},
+                       {"ub", ub, bpitch, bstride}, {"vb", vb, bpitch, bstride},
+                       {"uc", uc, cpitch, cstride}, {"vc", vc, cpitch, cstride}};
+  // c off b; c off a too, unless it runs in place on a: a px reads its own a and nobody else's
+  static constexpr Overlap ov[8] = {{4, 2}, {4, 3}, {5, 2}, {5, 3},
+                                    {4, 0, true}, {4, 1, true}, {5, 0, true}, {5, 1, true}};
   const bool in_place = uc == ua && vc == va && cpitch == apitch && cstride == astride;
-  if (!in_place)
-    for (int i = 4; i < 6; ++i)
-      for (int k = 0; k < 2; ++k)
-        if (fb_overlap(pl[i], pl[k], n, w, h))
-          return set_err(c, TVL1_EINVAL, "%s overlaps %s without being flow a itself", pl[i].name,
-                         pl[k].name);
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long *cnt = nullptr;
-  if (outside) {
-    order_streams(c, st);
-    if (!c->retired.empty()) reap_retired(c, false);
-    const size_t need = kFbChunk * sizeof(unsigned long long);
-    if (need > c->compose_bytes)
-      TVL1_TRY(arena_alloc(c, &c->compose_counts, &c->compose_bytes, need, st));
-    cnt = reinterpret_cast<unsigned long long *>(c->compose_counts);
-  }
-  const size_t tok = xprof_begin(c, st);
-  for (int32_t b = 0; b < n; b += kFbChunk) {
-    const int m = std::min(kFbChunk, n - b);
-    // the next chunk's zero fill is in stream order behind this one's copy
-    if (cnt) HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(unsigned long long), st));
+  const PlaneSet ps = {n, w, h, pl, 6, -1};
+  std::string msg;
+  TVL1_TRY(planes_try(c, check_planes(ps, kFloatXLimit, &msg), msg));
+  TVL1_TRY(planes_try(c, check_overlaps(ps, ov, 8, in_place, &msg), msg));
+  return run_chunks(c, stream, n, 24.0 * w * h * n, outside, sizeof(uint64_t),
+                    [&](int32_t b, int m, unsigned long long *cnt) {
     ComposeArgs a;
-    a.ua = reinterpret_cast<const float *>(reinterpret_cast<const char *>(ua) + (size_t)b * astride);
-    a.va = reinterpret_cast<const float *>(reinterpret_cast<const char *>(va) + (size_t)b * astride);
-    a.ub = reinterpret_cast<const float *>(reinterpret_cast<const char *>(ub) + (size_t)b * bstride);
-    a.vb = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vb) + (size_t)b * bstride);
-    a.uc = reinterpret_cast<float *>(reinterpret_cast<char *>(uc) + (size_t)b * cstride);
-    a.vc = reinterpret_cast<float *>(reinterpret_cast<char *>(vc) + (size_t)b * cstride);
+    a.ua = pair_at(ua, b, astride), a.va = pair_at(va, b, astride);
+    a.ub = pair_at(ub, b, bstride), a.vb = pair_at(vb, b, bstride);
+    a.uc = pair_at(uc, b, cstride), a.vc = pair_at(vc, b, cstride);
     a.ap = apitch, a.as = astride, a.bp = bpitch, a.bs = bstride, a.cp = cpitch, a.cs = cstride;
     a.w = w, a.h = h, a.count = cnt;
-    hipLaunchKernelGGL(k_compose_flow, fb_grid(w, h, m), kBlk2, 0, st, a);
-    if (cnt)
-      HIP_TRY(c, hipMemcpyAsync(outside + b, cnt, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  }
-  xprof_end(c, st, tok, 24.0 * w * h * n);
-  HIP_TRY(c, hipGetLastError());
-  if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
-  return TVL1_OK;
+    hipLaunchKernelGGL(k_compose_flow, fb_grid(w, h, m), kBlk2, 0, (hipStream_t)stream, a);
+  });
 }
 
 tvl1_status tvl1_compose_flow(tvl1_ctx *c, const float *ua, const float *va, size_t apitch,
@@ -3415,54 +3366,32 @@ tvl1_status tvl1_invert_flow_batch(tvl1_ctx *c, int32_t n, const float *uf, cons
                                    float *ug, float *vg, size_t gpitch, size_t gstride, float *resid,
                                    size_t rpitch, size_t rstride, int32_t w, int32_t h,
                                    tvl1_invert_counts *counts, void *stream) {
-  const FbPlane pl[5] = {{"uf", uf, fpitch, fstride}, {"vf", vf, fpitch, fstride},
-                         {"ug", ug, gpitch, gstride}, {"vg", vg, gpitch, gstride},
-                         {"resid", resid, rpitch, rstride}};
-  const int np = resid ? 5 : 4;
-  TVL1_TRY(check_fb(c, n, w, h, pl, np));
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  const Plane pl[5] = {{"uf", uf, fpitch, fstride}, {"vf", vf, fpitch, fstride},
+                       {"ug", ug, gpitch, gstride}, {"vg", vg, gpitch, gstride},
+                       {"resid", resid, rpitch, rstride}};
+  // a px reads f at other px: nothing runs in place, every output off every plane before it
+  static constexpr Overlap ov[9] = {{2, 0}, {2, 1}, {3, 0}, {3, 1}, {3, 2}, {4, 0}, {4, 1}, {4, 2}, {4, 3}};
+  const PlaneSet ps = {n, w, h, pl, 5, resid ? -1 : 4};
+  std::string msg;
+  TVL1_TRY(planes_try(c, check_planes(ps, kFloatXLimit, &msg), msg));
   if (iterations < 1 || iterations > kInvMaxIter)
     return set_err(c, TVL1_EINVAL, "iterations must be 1..%d (got %d)", kInvMaxIter, iterations);
   if (std::isnan(tol)) return set_err(c, TVL1_EINVAL, "tol is NaN");
-  // a px reads f at other px: nothing runs in place
-  for (int i = 2; i < np; ++i)
-    for (int k = 0; k < i; ++k)
-      if (fb_overlap(pl[i], pl[k], n, w, h))
-        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[i].name, pl[k].name);
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long *cnt = nullptr;
-  if (counts) {
-    order_streams(c, st);
-    if (!c->retired.empty()) reap_retired(c, false);
-    const size_t need = kFbChunk * sizeof(tvl1_invert_counts);
-    if (need > c->invert_bytes) TVL1_TRY(arena_alloc(c, &c->invert_counts, &c->invert_bytes, need, st));
-    cnt = reinterpret_cast<unsigned long long *>(c->invert_counts);
-  }
-  const size_t tok = xprof_begin(c, st);
-  for (int32_t b = 0; b < n; b += kFbChunk) {
-    const int m = std::min(kFbChunk, n - b);
-    // the next chunk's zero fill is in stream order behind this one's copy
-    if (cnt) HIP_TRY(c, hipMemsetAsync(cnt, 0, (size_t)m * sizeof(tvl1_invert_counts), st));
+  TVL1_TRY(planes_try(c, check_overlaps(ps, ov, 9, false, &msg), msg));
+  return run_chunks(c, stream, n, 20.0 * w * h * n, counts, sizeof(tvl1_invert_counts),
+                    [&](int32_t b, int m, unsigned long long *cnt) {
     InvertArgs a;
-    a.uf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(uf) + (size_t)b * fstride);
-    a.vf = reinterpret_cast<const float *>(reinterpret_cast<const char *>(vf) + (size_t)b * fstride);
-    a.ug = reinterpret_cast<float *>(reinterpret_cast<char *>(ug) + (size_t)b * gstride);
-    a.vg = reinterpret_cast<float *>(reinterpret_cast<char *>(vg) + (size_t)b * gstride);
-    a.resid = resid ? reinterpret_cast<float *>(reinterpret_cast<char *>(resid) + (size_t)b * rstride) : nullptr;
+    a.uf = pair_at(uf, b, fstride), a.vf = pair_at(vf, b, fstride);
+    a.ug = pair_at(ug, b, gstride), a.vg = pair_at(vg, b, gstride);
+    a.resid = resid ? pair_at(resid, b, rstride) : nullptr;
     a.fp = fpitch, a.fs = fstride, a.gp = gpitch, a.gs = gstride, a.rp = rpitch, a.rs = rstride;
     a.w = w, a.h = h, a.iters = iterations, a.tol = tol, a.count = cnt;
     if (c->invert_window)
-      hipLaunchKernelGGL(k_invert_flow<true>, fb_grid(w, h, m), kBlk2, 0, st, a);
+      hipLaunchKernelGGL(k_invert_flow<true>, fb_grid(w, h, m), kBlk2, 0, (hipStream_t)stream, a);
     else
-      hipLaunchKernelGGL(k_invert_flow<false>, fb_grid(w, h, m), kBlk2, 0, st, a);
-    if (cnt)
-      HIP_TRY(c, hipMemcpyAsync(counts + b, cnt, (size_t)m * sizeof(tvl1_invert_counts),
-                                hipMemcpyDeviceToHost, st));
-  }
-  xprof_end(c, st, tok, 20.0 * w * h * n);
-  HIP_TRY(c, hipGetLastError());
-  if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
-  return TVL1_OK;
+      hipLaunchKernelGGL(k_invert_flow<false>, fb_grid(w, h, m), kBlk2, 0, (hipStream_t)stream, a);
+  });
 }
 
 tvl1_status tvl1_invert_flow(tvl1_ctx *c, const float *uf, const float *vf, size_t fpitch,
@@ -3475,53 +3404,6 @@ tvl1_status tvl1_invert_flow(tvl1_ctx *c, const float *uf, const float *vf, size
 
 // ---- Photometric (ZNCC) score of a flow (added under ABI 9; kernels in tvl1_score.hpp,
 // DESIGN 14) ----
-static constexpr int32_t kZnMaxDim = 1 << 19;   // mx * 32 is an exact integer below 2^24
-
-// A plane of each of n pairs (rows of `row` bytes): its span in bytes over the whole batch
-struct ZnPlane {
-  const char *name;
-  const void *p;
-  size_t pitch, stride, row;
-};
-
-static bool zn_overlap(const ZnPlane &a, const ZnPlane &b, int32_t n, int32_t h) {
-  auto span = [&](const ZnPlane &q, uintptr_t &lo, uintptr_t &hi) {
-    lo = reinterpret_cast<uintptr_t>(q.p);
-    hi = lo + (size_t)(n - 1) * q.stride + q.pitch * (size_t)(h - 1) + q.row;
-  };
-  uintptr_t a0, a1, b0, b1;
-  span(a, a0, a1);
-  span(b, b0, b1);
-  return a0 < b1 && b0 < a1;
-}
-
-// What the three calls check about sizes and planes, before anything is launched: nu8 u8 planes
-// first (a pair stride 0 is one shared plane where `shared_ok`), f32 planes after them
-static tvl1_status check_zn(tvl1_ctx *c, int32_t n, int32_t w, int32_t h, const ZnPlane *pl, int np,
-                            int nu8, bool shared_ok) {
-  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
-  for (int i = 0; i < np; ++i)
-    if (!pl[i].p) return set_err(c, TVL1_EINVAL, "%s is NULL", pl[i].name);
-  if (n < 1) return set_err(c, TVL1_EINVAL, "n must be >= 1 (got %d)", n);
-  if (w < 1 || h < 1) return set_err(c, TVL1_EINVAL, "bad size %dx%d", w, h);
-  if (w > kZnMaxDim || h > kZnMaxDim)
-    return set_err(c, TVL1_ESIZE, "size %dx%d above 2^19 (the 1/32 px map is no longer exact)", w, h);
-  for (int i = 0; i < np; ++i) {
-    if (i < nu8) {
-      if (pl[i].pitch < (size_t)w) return set_err(c, TVL1_EINVAL, "%s: pitch must be >= w", pl[i].name);
-      if (shared_ok && pl[i].stride == 0) continue;
-    } else {
-      if (pl[i].pitch % 4 || pl[i].pitch < (size_t)w * sizeof(float))
-        return set_err(c, TVL1_EINVAL, "%s: pitch must be a multiple of 4 and >= 4 * w", pl[i].name);
-      if (pl[i].stride % 4)
-        return set_err(c, TVL1_EINVAL, "%s: pair stride must be a multiple of 4", pl[i].name);
-    }
-    if (n > 1 && pl[i].stride < pl[i].pitch * (size_t)(h - 1) + pl[i].row)
-      return set_err(c, TVL1_EINVAL, "%s: pair stride must cover one plane", pl[i].name);
-  }
-  return TVL1_OK;
-}
-
 static void launch_zncc(const ZnccArgs &a, int radius, int m, hipStream_t st) {
   const int bw = 64 - 2 * radius, bands = (a.w + bw - 1) / bw;   // a band's output columns
   const dim3 grid((unsigned)((bands + 3) / 4), (unsigned)((a.h + kZnSegRows - 1) / kZnSegRows), (unsigned)m);
@@ -3538,32 +3420,25 @@ tvl1_status tvl1_zncc_score_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, siz
                                   const float *u, const float *v, size_t fpitch, size_t fstride,
                                   int32_t w, int32_t h, int32_t radius, float *score, size_t spitch,
                                   size_t sstride, void *stream) {
-  const size_t rb = w > 0 ? (size_t)w : 0;
-  const ZnPlane pl[5] = {{"I0", I0, pitch0, stride0, rb}, {"I1", I1, pitch1, stride1, rb},
-                         {"u", u, fpitch, fstride, 4 * rb}, {"v", v, fpitch, fstride, 4 * rb},
-                         {"score", score, spitch, sstride, 4 * rb}};
-  TVL1_TRY(check_zn(c, n, w, h, pl, 5, 2, true));
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  const Plane pl[5] = {{"I0", I0, pitch0, stride0, 1, true}, {"I1", I1, pitch1, stride1, 1, true},
+                       {"u", u, fpitch, fstride}, {"v", v, fpitch, fstride},
+                       {"score", score, spitch, sstride}};
+  static constexpr Overlap ov[4] = {{4, 0}, {4, 1}, {4, 2}, {4, 3}};
+  const PlaneSet ps = {n, w, h, pl, 5, -1};
+  std::string msg;
+  TVL1_TRY(planes_try(c, check_planes(ps, kMap32Limit, &msg), msg));
   if (radius < 1 || radius > 4) return set_err(c, TVL1_EINVAL, "radius must be 1..4 (got %d)", radius);
-  for (int i = 0; i < 4; ++i)
-    if (zn_overlap(pl[4], pl[i], n, h)) return set_err(c, TVL1_EINVAL, "score overlaps %s", pl[i].name);
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t tok = xprof_begin(c, st);
-  for (int32_t b = 0; b < n; b += kFbChunk) {
-    const int m = std::min(kFbChunk, n - b);
+  TVL1_TRY(planes_try(c, check_overlaps(ps, ov, 4, false, &msg), msg));
+  return run_chunks(c, stream, n, 14.0 * w * h * n, nullptr, 0, [&](int32_t b, int m, unsigned long long *) {
     ZnccArgs a;
-    a.I0 = I0 + (size_t)b * stride0, a.I1 = I1 + (size_t)b * stride1;
-    a.u = reinterpret_cast<const float *>(reinterpret_cast<const char *>(u) + (size_t)b * fstride);
-    a.v = reinterpret_cast<const float *>(reinterpret_cast<const char *>(v) + (size_t)b * fstride);
-    a.score = reinterpret_cast<float *>(reinterpret_cast<char *>(score) + (size_t)b * sstride);
+    a.I0 = pair_at(I0, b, stride0), a.I1 = pair_at(I1, b, stride1);
+    a.u = pair_at(u, b, fstride), a.v = pair_at(v, b, fstride), a.score = pair_at(score, b, sstride);
     a.p0 = pitch0, a.s0 = stride0, a.p1 = pitch1, a.s1 = stride1;
     a.fp = fpitch, a.fs = fstride, a.sp = spitch, a.ss = sstride;
     a.w = w, a.h = h;
-    launch_zncc(a, radius, m, st);
-  }
-  xprof_end(c, st, tok, 14.0 * w * h * n);
-  HIP_TRY(c, hipGetLastError());
-  return TVL1_OK;
+    launch_zncc(a, radius, m, (hipStream_t)stream);
+  });
 }
 
 tvl1_status tvl1_zncc_score(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const uint8_t *I1,
@@ -3576,30 +3451,24 @@ tvl1_status tvl1_zncc_score(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, const
 tvl1_status tvl1_warp_by_flow_u8(tvl1_ctx *c, const uint8_t *I1, size_t pitch1, const float *u,
                                  const float *v, size_t fpitch, int32_t w, int32_t h, uint8_t *dst,
                                  size_t dpitch, uint8_t *valid, size_t vpitch, void *stream) {
-  const size_t rb = w > 0 ? (size_t)w : 0;
-  // u8 planes first; `valid` only where it is given
-  const ZnPlane pl[5] = {{"I1", I1, pitch1, 0, rb}, {"dst", dst, dpitch, 0, rb},
-                         {"valid", valid ? valid : dst, valid ? vpitch : dpitch, 0, rb},
-                         {"u", u, fpitch, 0, 4 * rb}, {"v", v, fpitch, 0, 4 * rb}};
-  TVL1_TRY(check_zn(c, 1, w, h, pl, 5, 3, false));
-  const int in[3] = {0, 3, 4};
-  for (int o = 1; o < (valid ? 3 : 2); ++o)   // each output against each input
-    for (int i : in)
-      if (zn_overlap(pl[o], pl[i], 1, h))
-        return set_err(c, TVL1_EINVAL, "%s overlaps %s", pl[o].name, pl[i].name);
-  if (valid && zn_overlap(pl[1], pl[2], 1, h)) return set_err(c, TVL1_EINVAL, "valid overlaps dst");
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  const size_t tok = xprof_begin(c, st);
-  WarpFlowArgs a;
-  a.I1 = I1, a.p1 = pitch1, a.u = u, a.v = v, a.fp = fpitch, a.w = w, a.h = h;
-  a.dst = dst, a.dp = dpitch, a.valid = valid, a.vp = vpitch;
-  const dim3 grid((unsigned)((w + 64 * kFbPx - 1) / (64 * kFbPx)), 1u,
-                  (unsigned)std::min((h + 3) / 4, kZnMaxRowGroups));
-  hipLaunchKernelGGL(k_warp_flow_u8, grid, kBlk2, 0, st, a);
-  xprof_end(c, st, tok, (valid ? 11.0 : 10.0) * w * h);
-  HIP_TRY(c, hipGetLastError());
-  return TVL1_OK;
+  if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
+  const Plane pl[5] = {{"I1", I1, pitch1, 0, 1}, {"dst", dst, dpitch, 0, 1},
+                       {"valid", valid, vpitch, 0, 1},   // left out where it is not given
+                       {"u", u, fpitch, 0}, {"v", v, fpitch, 0}};
+  // each output off each input, then off each other
+  static constexpr Overlap ov[7] = {{1, 0}, {1, 3}, {1, 4}, {2, 0}, {2, 3}, {2, 4}, {2, 1}};
+  const PlaneSet ps = {1, w, h, pl, 5, valid ? -1 : 2};
+  std::string msg;
+  TVL1_TRY(planes_try(c, check_planes(ps, kMap32Limit, &msg), msg));
+  TVL1_TRY(planes_try(c, check_overlaps(ps, ov, 7, false, &msg), msg));
+  return run_chunks(c, stream, 1, (valid ? 11.0 : 10.0) * w * h, nullptr, 0, [&](int32_t, int, unsigned long long *) {
+    WarpFlowArgs a;
+    a.I1 = I1, a.p1 = pitch1, a.u = u, a.v = v, a.fp = fpitch, a.w = w, a.h = h;
+    a.dst = dst, a.dp = dpitch, a.valid = valid, a.vp = vpitch;
+    const dim3 grid((unsigned)((w + 64 * kFbPx - 1) / (64 * kFbPx)), 1u,
+                    (unsigned)std::min((h + 3) / 4, kZnMaxRowGroups));
+    hipLaunchKernelGGL(k_warp_flow_u8, grid, kBlk2, 0, (hipStream_t)stream, a);
+  });
 }
 
 void *tvl1_stream(tvl1_ctx *c) { return c ? (void *)c->own_stream : nullptr; }
@@ -3629,9 +3498,7 @@ void tvl1_destroy(tvl1_ctx *c) {
   if (c->small_scratch) (void)hipFree(c->small_scratch);
   if (c->shift_scratch) (void)hipFree(c->shift_scratch);
   if (c->seed_scratch) (void)hipFree(c->seed_scratch);
-  if (c->fb_counts) (void)hipFree(c->fb_counts);
-  if (c->compose_counts) (void)hipFree(c->compose_counts);
-  if (c->invert_counts) (void)hipFree(c->invert_counts);
+  if (c->count_scratch) (void)hipFree(c->count_scratch);
   for (auto &r : c->retired) free_retired(r);
   if (c->align_pat) (void)hipFree(c->align_pat);
   if (c->pinned) (void)hipHostFree(c->pinned);

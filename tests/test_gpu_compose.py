@@ -4,10 +4,13 @@ composition is one IEEE rounding per operation in a fixed order, so every finite
 infinity must be equal and a NaN must be a NaN; the outside counts must be equal; no float outside
 a ROI view may change; in place must equal out of place.  Holds on a ctx with fast_math = 1 and
 on one with profile = 1 alike."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
 import compose_cases as T
+import flowop_badargs as B
 import compose_ref as ref
 from optflow_amd import capi
 
@@ -170,8 +173,10 @@ def test_profiled_calls_count_into_class_2_of_the_next_solve(built):
 
 
 def test_bad_arguments_return_before_a_launch(eng0):
+    """The rows of tests/flowop_badargs.py: each raises its status, with the message recorded
+    before the checks moved into csrc/tvl1_planes.hpp, and nothing runs."""
     e = eng0
-    W, H = 20, 6
+    W, H = B.W, B.H
     case = T.Case("err", W, H, "smooth", n=2)
     pl = T.planes(case)
     d = [Planes(a) for a in pl]
@@ -179,34 +184,21 @@ def test_bad_arguments_return_before_a_launch(eng0):
     cv = Planes(np.full(pl[0].shape, SENTINEL, np.float32))
     big = Planes(np.full((1, 2 * H + 1, W), SENTINEL, np.float32))   # for overlapping views
     torch.cuda.synchronize()
-    P, S = 4 * W, 4 * W * H
-    BIG = (1 << 24) + 1
+    assert (d[0].pitch, d[0].stride) == (B.P, B.S)
+    A = SimpleNamespace(d0=d[0].ptr, d1=d[1].ptr, d2=d[2].ptr, d3=d[3].ptr, cu=cu.ptr, cv=cv.ptr, big=big.ptr)
+    good = B.defaults("compose", A)["comp"]
 
-    def comp(n=2, ua=d[0].ptr, va=d[1].ptr, ap=P, as_=S, ub=d[2].ptr, vb=d[3].ptr, bp=P, bs=S, w=W,
-             h=H, uc=cu.ptr, vc=cv.ptr, cp=P, cs=S):
-        return e.compose_flow_batch(n, ua, va, ap, as_, ub, vb, bp, bs, w, h, uc, vc, cp, cs,
-                                    stream=e.stream)
+    def comp(**kw):
+        a = {**good, **kw}
+        return e.compose_flow_batch(*(a[k] for k in ("n", "ua", "va", "ap", "as_", "ub", "vb", "bp", "bs", "w",
+                                                     "h", "uc", "vc", "cp", "cs")), stream=e.stream)
 
-    einval = [
-        dict(ua=0), dict(va=0), dict(ub=0), dict(vb=0), dict(uc=0), dict(vc=0),
-        dict(n=0), dict(n=-3), dict(w=0), dict(h=0), dict(w=-1), dict(h=-2),
-        dict(ap=P - 4), dict(bp=P - 4), dict(cp=P - 4), dict(ap=P + 2), dict(bp=P + 1), dict(cp=P + 3),
-        dict(as_=S + 2), dict(bs=S + 1), dict(cs=S + 3),            # strides that are no multiple of 4
-        dict(as_=S - 4), dict(bs=S - 4), dict(cs=S - 4), dict(cs=0),   # ... that do not cover a plane
-        dict(uc=d[2].ptr), dict(vc=d[3].ptr), dict(uc=d[3].ptr + 4), dict(vc=d[2].ptr + S),   # c over b
-        dict(n=1, uc=big.ptr, ub=big.ptr + P * H - 4),                 # ... by one float
-        # c over a other than a exactly: one plane only, swapped, shifted, another pitch or stride
-        dict(uc=d[0].ptr), dict(vc=d[1].ptr), dict(uc=d[1].ptr, vc=d[0].ptr),
-        dict(uc=d[0].ptr + 4, vc=d[1].ptr), dict(n=1, uc=d[0].ptr, vc=d[1].ptr, cs=S + 4),
-        dict(n=1, ua=big.ptr, va=d[1].ptr, ap=2 * P, uc=big.ptr, vc=d[1].ptr, cp=P),
-        dict(n=1, ua=big.ptr, uc=big.ptr + P * H - 4),
-    ]
-    for kw in einval:
-        with pytest.raises(capi.TVL1Error, match="TVL1_EINVAL"):
+    messages = []
+    for _, kw, status in B.rows("compose", A):
+        with pytest.raises(capi.TVL1Error, match=status) as err:
             comp(**kw)
-    for kw in [dict(w=BIG, ap=4 * BIG, bp=4 * BIG, cp=4 * BIG, n=1), dict(h=BIG, n=1)]:
-        with pytest.raises(capi.TVL1Error, match="TVL1_ESIZE"):
-            comp(**kw)
+        messages.append(str(err.value))
+    B.assert_recorded("compose", messages)
     torch.cuda.synchronize()
     # nothing ran: every plane is what it was
     assert np.all(cu.get()[0] == SENTINEL) and np.all(cv.get()[0] == SENTINEL)

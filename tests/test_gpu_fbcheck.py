@@ -3,10 +3,13 @@ tests/fbcheck_ref.py (numpy float32) on every case of tests/fbcheck_cases.py: th
 IEEE rounding per operation in a fixed order, so every finite value and every infinity must be
 equal and a NaN must be a NaN; tvl1_zero_above must zero exactly the restatement's px and count
 them.  Holds on a ctx with fast_math = 1 and on one with profile = 1 alike."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
 import fbcheck_cases as T
+import flowop_badargs as B
 import fbcheck_ref as ref
 from optflow_amd import capi
 
@@ -165,48 +168,36 @@ def test_profiled_calls_count_into_class_2_of_the_next_solve(eng0):
 
 
 def test_bad_arguments_return_before_a_launch(eng0):
+    """The rows of tests/flowop_badargs.py: each raises its status, with the message recorded
+    before the checks moved into csrc/tvl1_planes.hpp, and nothing runs."""
     e = eng0
-    W, H = 20, 6
+    W, H = B.W, B.H
     case = T.Case("err", W, H, "smooth", 0.01, 0.5, n=2)
     pl = T.planes(case)
     d = [Planes(a) for a in pl]
     s = Planes(np.full(pl[0].shape, SENTINEL, np.float32))
     big = Planes(np.full((1, 2 * H + 1, W), SENTINEL, np.float32))   # for overlapping views
     torch.cuda.synchronize()
-    P, S = 4 * W, 4 * W * H
+    assert (d[0].pitch, d[0].stride) == (B.P, B.S)
+    A = SimpleNamespace(d0=d[0].ptr, d1=d[1].ptr, d2=d[2].ptr, d3=d[3].ptr, s=s.ptr, big=big.ptr)
+    good = B.defaults("fbcheck", A)
 
-    def score(n=2, uf=d[0].ptr, vf=d[1].ptr, fp=P, fs=S, ub=d[2].ptr, vb=d[3].ptr, bp=P, bs=S, w=W, h=H,
-              alpha=0.01, sc=s.ptr, sp=P, ss=S):
-        e.fb_score_batch(n, uf, vf, fp, fs, ub, vb, bp, bs, w, h, alpha, sc, sp, ss, stream=e.stream)
+    def score(**kw):
+        a = {**good["score"], **kw}
+        e.fb_score_batch(*(a[k] for k in ("n", "uf", "vf", "fp", "fs", "ub", "vb", "bp", "bs", "w", "h", "alpha",
+                                          "sc", "sp", "ss")), stream=e.stream)
 
-    def zero(n=2, u=d[0].ptr, v=d[1].ptr, fp=P, fs=S, sc=s.ptr, sp=P, ss=S, w=W, h=H, beta=0.5):
-        e.zero_above_batch(n, u, v, fp, fs, sc, sp, ss, w, h, beta, stream=e.stream)
+    def zero(**kw):
+        a = {**good["zero"], **kw}
+        e.zero_above_batch(*(a[k] for k in ("n", "u", "v", "fp", "fs", "sc", "sp", "ss", "w", "h", "beta")),
+                           stream=e.stream)
 
-    einval = [
-        (score, dict(uf=0)), (score, dict(vf=0)), (score, dict(ub=0)), (score, dict(vb=0)),
-        (score, dict(sc=0)), (score, dict(n=0)), (score, dict(n=-3)), (score, dict(w=0)),
-        (score, dict(h=0)), (score, dict(w=-1)), (score, dict(fp=P - 4)), (score, dict(bp=P + 2)),
-        (score, dict(sp=P - 4)), (score, dict(sp=P + 1)), (score, dict(fs=S + 2)),
-        (score, dict(bs=S + 1)), (score, dict(ss=S + 3)), (score, dict(fs=S - 4)),
-        (score, dict(alpha=float("nan"))),
-        (score, dict(sc=d[0].ptr)), (score, dict(sc=d[3].ptr + 4)),     # score over a flow plane
-        (score, dict(n=1, sc=big.ptr, uf=big.ptr + P * H - 4)),         # ... by one float
-        (score, dict(ub=d[0].ptr)), (score, dict(vb=d[1].ptr + S)),     # backward over forward
-        (zero, dict(u=0)), (zero, dict(v=0)), (zero, dict(sc=0)), (zero, dict(n=0)),
-        (zero, dict(w=0)), (zero, dict(h=-2)), (zero, dict(fp=P - 4)), (zero, dict(fp=P + 2)),
-        (zero, dict(sp=P - 4)), (zero, dict(fs=S + 2)), (zero, dict(ss=S + 1)),
-        (zero, dict(beta=float("nan"))), (zero, dict(sc=d[0].ptr)), (zero, dict(sc=d[1].ptr + S)),
-    ]
-    for fn, kw in einval:
-        with pytest.raises(capi.TVL1Error, match="TVL1_EINVAL"):
-            fn(**kw)
-    for fn, kw in [(score, dict(w=(1 << 24) + 1, fp=4 * ((1 << 24) + 1), bp=4 * ((1 << 24) + 1),
-                                sp=4 * ((1 << 24) + 1), n=1)),
-                   (score, dict(h=(1 << 24) + 1, n=1)),
-                   (zero, dict(h=(1 << 24) + 1, n=1)),
-                   (zero, dict(w=(1 << 24) + 1, fp=4 * ((1 << 24) + 1), sp=4 * ((1 << 24) + 1), n=1))]:
-        with pytest.raises(capi.TVL1Error, match="TVL1_ESIZE"):
-            fn(**kw)
+    fns, messages = dict(score=score, zero=zero), []
+    for call, kw, status in B.rows("fbcheck", A):
+        with pytest.raises(capi.TVL1Error, match=status) as err:
+            fns[call](**kw)
+        messages.append(str(err.value))
+    B.assert_recorded("fbcheck", messages)
     torch.cuda.synchronize()
     # nothing ran: every output is what it was
     assert np.all(s.get()[0] == SENTINEL) and np.all(big.get()[0] == SENTINEL)

@@ -5,10 +5,13 @@ infinity must be equal and a NaN must be a NaN; the outside and unconverged coun
 no float outside a ROI view may change and f stays what it was.  Holds on a ctx with fast_math = 1
 and on one with profile = 1 alike, and on both arms of the kernel (TVL1_INVERT_WINDOW = 0 / 1,
 read when the ctx is created)."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
 import compose_ref as cref
+import flowop_badargs as B
 import invert_cases as T
 import invert_ref as ref
 from optflow_amd import capi
@@ -199,8 +202,10 @@ def test_profiled_calls_count_into_class_2_of_the_next_solve(built):
 
 
 def test_bad_arguments_return_before_a_launch(eng0):
+    """The rows of tests/flowop_badargs.py: each raises its status, with the message recorded
+    before the checks moved into csrc/tvl1_planes.hpp, and nothing runs."""
     e = eng0
-    W, H = 20, 6
+    W, H = B.W, B.H
     case = T.Case("err", W, H, "smooth", 2, n=2)
     pl = T.planes(case)
     d = [Planes(a) for a in pl]
@@ -208,35 +213,22 @@ def test_bad_arguments_return_before_a_launch(eng0):
     gu, gv, rs = Planes(blank), Planes(blank), Planes(blank)
     big = Planes(np.full((1, 2 * H + 1, W), SENTINEL, np.float32))   # for overlapping views
     torch.cuda.synchronize()
-    P, S = 4 * W, 4 * W * H
-    BIG = (1 << 24) + 1
+    P = B.P
+    assert (d[0].pitch, d[0].stride) == (B.P, B.S)
+    A = SimpleNamespace(d0=d[0].ptr, d1=d[1].ptr, gu=gu.ptr, gv=gv.ptr, rs=rs.ptr, big=big.ptr)
+    good = B.defaults("invert", A)["inv"]
 
-    def inv(n=2, uf=d[0].ptr, vf=d[1].ptr, fp=P, fs=S, K=2, tol=0.01, ug=gu.ptr, vg=gv.ptr, gp=P, gs=S,
-            r=rs.ptr, rp=P, rs_=S, w=W, h=H):
-        return e.invert_flow_batch(n, uf, vf, fp, fs, K, tol, ug, vg, gp, gs, r, rp, rs_, w, h,
-                                   stream=e.stream)
+    def inv(**kw):
+        a = {**good, **kw}
+        return e.invert_flow_batch(*(a[k] for k in ("n", "uf", "vf", "fp", "fs", "K", "tol", "ug", "vg", "gp",
+                                                    "gs", "r", "rp", "rs_", "w", "h")), stream=e.stream)
 
-    einval = [
-        dict(uf=0), dict(vf=0), dict(ug=0), dict(vg=0),
-        dict(n=0), dict(n=-3), dict(w=0), dict(h=0), dict(w=-1), dict(h=-2),
-        dict(K=0), dict(K=-1), dict(K=33), dict(tol=float("nan")),
-        dict(fp=P - 4), dict(gp=P - 4), dict(rp=P - 4), dict(fp=P + 2), dict(gp=P + 1), dict(rp=P + 3),
-        dict(fs=S + 2), dict(gs=S + 1), dict(rs_=S + 3),            # strides that are no multiple of 4
-        dict(fs=S - 4), dict(gs=S - 4), dict(rs_=S - 4), dict(gs=0),   # ... that do not cover a plane
-        # g over f: exactly (nothing runs in place), swapped, shifted, by one float
-        dict(ug=d[0].ptr), dict(vg=d[1].ptr), dict(ug=d[0].ptr, vg=d[1].ptr), dict(ug=d[1].ptr, vg=d[0].ptr),
-        dict(ug=d[0].ptr + 4), dict(vg=d[1].ptr + S), dict(n=1, uf=big.ptr, ug=big.ptr + P * H - 4),
-        dict(n=1, ug=big.ptr, uf=big.ptr + P * H - 4),
-        # resid over f or g, and ug over vg
-        dict(r=d[0].ptr), dict(r=d[1].ptr + 4), dict(r=gu.ptr), dict(r=gv.ptr + S), dict(ug=gv.ptr),
-        dict(n=1, ug=big.ptr, r=big.ptr + P * H - 4), dict(n=1, vg=big.ptr, ug=big.ptr + P * H - 4),
-    ]
-    for kw in einval:
-        with pytest.raises(capi.TVL1Error, match="TVL1_EINVAL"):
+    messages = []
+    for _, kw, status in B.rows("invert", A):
+        with pytest.raises(capi.TVL1Error, match=status) as err:
             inv(**kw)
-    for kw in [dict(w=BIG, fp=4 * BIG, gp=4 * BIG, rp=4 * BIG, n=1), dict(h=BIG, n=1)]:
-        with pytest.raises(capi.TVL1Error, match="TVL1_ESIZE"):
-            inv(**kw)
+        messages.append(str(err.value))
+    B.assert_recorded("invert", messages)
     torch.cuda.synchronize()
     # nothing ran: every plane is what it was
     for p in (gu, gv, rs, big):

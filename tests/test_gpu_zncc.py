@@ -4,9 +4,12 @@ score is four IEEE f64 operations and one conversion, so every finite value and 
 be equal.  Holds on a ctx with fast_math = 1 and on one with profile = 1 alike.  ROI views lie
 in allocations filled with values that would change a sum if they were read, and the score's
 allocation must be untouched outside the ROI."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
+import flowop_badargs as B
 import zncc_cases as T
 import zncc_ref as ref
 from optflow_amd import capi
@@ -180,8 +183,10 @@ def test_profiled_calls_count_into_class_2_of_the_next_solve(built):
 
 
 def test_bad_arguments_return_before_a_launch(eng0):
+    """The rows of tests/flowop_badargs.py: each raises its status, with the message recorded
+    before the checks moved into csrc/tvl1_planes.hpp, and nothing runs."""
     e = eng0
-    W, H = 20, 6
+    W, H = B.W, B.H
     case = T.Case("err", W, H, "smooth", 2, n=2)
     pl = T.planes(case)
     d = [Planes(a) for a in pl]
@@ -189,44 +194,27 @@ def test_bad_arguments_return_before_a_launch(eng0):
     big = Planes(np.full((1, 2 * H + 1, W), SENTINEL[np.dtype(F)], F))   # for overlapping views
     J = Planes(np.full((1, H, W), 99, np.uint8))
     torch.cuda.synchronize()
-    P, S, P8, S8 = 4 * W, d[2].stride, W, d[0].stride
-    assert S >= P * H and S8 >= P8 * H
+    assert (d[2].pitch, d[2].stride, d[0].pitch, d[0].stride) == (B.P, B.ZS, B.P8, B.S8)
+    assert B.ZS >= B.P * H and B.S8 >= B.P8 * H
+    A = SimpleNamespace(d0=d[0].ptr, d1=d[1].ptr, d2=d[2].ptr, d3=d[3].ptr, s=s.ptr, big=big.ptr, J=J.ptr)
+    good = B.defaults("zncc", A)
 
-    def score(n=2, i0=d[0].ptr, p0=P8, s0=S8, i1=d[1].ptr, p1=P8, s1=S8, u=d[2].ptr, v=d[3].ptr, fp=P,
-              fs=S, w=W, h=H, r=2, sc=s.ptr, sp=P, ss=S):
-        e.zncc_score_batch(n, i0, p0, s0, i1, p1, s1, u, v, fp, fs, w, h, r, sc, sp, ss, stream=e.stream)
+    def score(**kw):
+        a = {**good["score"], **kw}
+        e.zncc_score_batch(*(a[k] for k in ("n", "i0", "p0", "s0", "i1", "p1", "s1", "u", "v", "fp", "fs", "w",
+                                            "h", "r", "sc", "sp", "ss")), stream=e.stream)
 
-    def warp(i1=d[1].ptr, p1=P8, u=d[2].ptr, v=d[3].ptr, fp=P, w=W, h=H, dst=J.ptr, dp=P8, valid=0, vp=0):
-        e.warp_by_flow_u8(i1, p1, u, v, fp, w, h, dst, dp, valid, vp, stream=e.stream)
+    def warp(**kw):
+        a = {**good["warp"], **kw}
+        e.warp_by_flow_u8(*(a[k] for k in ("i1", "p1", "u", "v", "fp", "w", "h", "dst", "dp", "valid", "vp")),
+                          stream=e.stream)
 
-    einval = [
-        (score, dict(i0=0)), (score, dict(i1=0)), (score, dict(u=0)), (score, dict(v=0)),
-        (score, dict(sc=0)), (score, dict(n=0)), (score, dict(n=-3)), (score, dict(w=0)),
-        (score, dict(h=0)), (score, dict(w=-1)), (score, dict(r=0)), (score, dict(r=5)),
-        (score, dict(r=-1)), (score, dict(p0=W - 1)), (score, dict(p1=W - 1)),
-        (score, dict(fp=P - 4)), (score, dict(fp=P + 2)), (score, dict(sp=P - 4)),
-        (score, dict(sp=P + 1)), (score, dict(fs=S + 2)), (score, dict(ss=S + 3)),
-        (score, dict(fs=P * (H - 1))), (score, dict(ss=4)), (score, dict(s0=1)),
-        (score, dict(s1=P8 * (H - 1))),                                   # (a frame stride 0 is a shared frame)
-        (score, dict(sc=d[2].ptr)), (score, dict(sc=d[3].ptr + 4)),       # score over a flow plane
-        (score, dict(n=1, sc=big.ptr, u=big.ptr + P * H - 4)),            # ... by one float
-        (score, dict(n=1, sc=big.ptr, sp=P, i0=big.ptr + P * H - 1)),     # score over frame0, by one byte
-        (score, dict(n=1, sc=big.ptr, i1=big.ptr + 3)),                   # score over frame1
-        (warp, dict(i1=0)), (warp, dict(u=0)), (warp, dict(v=0)), (warp, dict(dst=0)),
-        (warp, dict(w=0)), (warp, dict(h=-2)), (warp, dict(p1=W - 1)), (warp, dict(dp=W - 1)),
-        (warp, dict(fp=P - 4)), (warp, dict(fp=P + 2)), (warp, dict(valid=J.ptr + 8, vp=W - 1)),
-        (warp, dict(dst=d[1].ptr)), (warp, dict(dst=d[2].ptr + 5)), (warp, dict(valid=d[3].ptr, vp=W)),
-        (warp, dict(valid=J.ptr + W * H - 1, vp=W)),                      # valid over dst by one byte
-    ]
-    for fn, kw in einval:
-        with pytest.raises(capi.TVL1Error, match="TVL1_EINVAL"):
-            fn(**kw)
-    big_w = (1 << 19) + 1
-    for fn, kw in [(score, dict(w=big_w, p0=big_w, p1=big_w, fp=4 * big_w, sp=4 * big_w, n=1)),
-                   (score, dict(h=big_w, n=1)), (warp, dict(h=big_w)),
-                   (warp, dict(w=big_w, p1=big_w, dp=big_w, fp=4 * big_w))]:
-        with pytest.raises(capi.TVL1Error, match="TVL1_ESIZE"):
-            fn(**kw)
+    fns, messages = dict(score=score, warp=warp), []
+    for call, kw, status in B.rows("zncc", A):
+        with pytest.raises(capi.TVL1Error, match=status) as err:
+            fns[call](**kw)
+        messages.append(str(err.value))
+    B.assert_recorded("zncc", messages)
     torch.cuda.synchronize()
     # nothing ran: every output is what it was
     assert np.all(s.get()[0] == SENTINEL[np.dtype(F)]) and np.all(big.get()[0] == SENTINEL[np.dtype(F)])
