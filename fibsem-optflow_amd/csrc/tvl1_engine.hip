@@ -23,6 +23,7 @@
 #include "../../include/tvl1.h"
 #include "tvl1_plan.hpp"
 #include "tvl1_walk.hpp"
+#include "tvl1_arena.hpp"
 #include "tvl1_kernels.hpp"
 #include "tvl1_batch.hpp"
 #include "tvl1_align_plan.hpp"
@@ -70,17 +71,76 @@ struct Geometry {
   bool gamma = false;
 };
 
+// tvl1_arena.hpp's backend: the HIP calls the memory lifecycle makes
+struct HipDev {
+  using Stream = hipStream_t;
+  using Event = hipEvent_t;
+  int malloc(char **p, size_t n) { return hipMalloc((void **)p, n); }
+  int free(char *p) { return hipFree(p); }
+  int memset_async(char *p, int v, size_t n, Stream s) { return hipMemsetAsync(p, v, n, s); }
+  int event_create(Event *e) { return hipEventCreateWithFlags(e, hipEventDisableTiming); }
+  int event_record(Event e, Stream s) { return hipEventRecord(e, s); }
+  int event_query(Event e) { return hipEventQuery(e); }
+  int event_sync(Event e) { return hipEventSynchronize(e); }
+  int event_destroy(Event e) { return e ? hipEventDestroy(e) : hipSuccess; }
+  int stream_wait(Stream s, Event e) { return hipStreamWaitEvent(s, e, 0); }
+  void clear_error() { (void)hipGetLastError(); }
+  const char *error_string(int e) { return hipGetErrorString((hipError_t)e); }
+};
+
+// Per-kernel-class HIP-event timing (tvl1_set_profiling): a pool of events, two per mark.
+struct MarkPool {
+  struct Mark {
+    int cls;
+    size_t a, b;
+    double bytes;      // SURVEY 8(d) algorithmic bytes
+    double hbm_bytes;  // compulsory bytes of this implementation
+  };
+  const size_t grow;        // events created when the pool runs short
+  const size_t max_marks;   // marks held; later ones are dropped (0: no bound)
+  std::vector<hipEvent_t> ev;
+  size_t used = 0;
+  std::vector<Mark> marks;
+
+  // the token of end(), 0 = not recording
+  size_t begin(bool profiling, hipStream_t st) {
+    if (!profiling || (max_marks && marks.size() >= max_marks)) return 0;
+    for (size_t i = 0; used + 2 > ev.size() && i < grow; ++i) {
+      hipEvent_t e;
+      // timing-only events: no system-scope fence (cache writeback + invalidate) at each
+      // record, which slowed the kernel after it and inflated the per-launch times ~6 %
+      // against the rocprofv3 kernel trace (r3)
+      if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) break;
+      ev.push_back(e);
+    }
+    if (used + 2 > ev.size()) return 0;
+    (void)hipEventRecord(ev[used], st);
+    return ++used;
+  }
+  void end(hipStream_t st, size_t tok, int cls, double bytes, double hbm_bytes = -1.0) {
+    if (tok == 0) return;
+    const size_t b = used++;
+    (void)hipEventRecord(ev[b], st);
+    marks.push_back({cls, tok - 1, b, bytes, hbm_bytes < 0 ? bytes : hbm_bytes});
+  }
+  void reset() {
+    marks.clear();
+    used = 0;
+  }
+  void destroy() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+};
+
 }  // namespace
 
 struct tvl1_ctx {
   int device = 0;
   tvl1_params prm{};
   std::string err;
-  hipStream_t own_stream = nullptr;
-
-  // arena
-  char *arena = nullptr;
-  size_t arena_bytes = 0;
+  // device memory (tvl1_arena.hpp): the lifecycle state and the own stream, then the blocks
+  Arena<HipDev> mem;
+  Block arena;                          // a single-pair solve's planes (ensure_geometry)
   Geometry geo;
   bool geo_valid = false;
 
@@ -104,16 +164,6 @@ struct tvl1_ctx {
   unsigned long long check_seq = 0;  // sequence number of the last residual check
   int poll = 1;                      // TVL1_POLL: wait for a residual by polling its
                                      // sequence number in host memory (0: event sync)
-  hipEvent_t ev_order = nullptr;  // orders work on the caller's stream after a zero fill
-  hipEvent_t ev_switch = nullptr; // orders a call on a new stream after the previous stream
-  hipStream_t last_stream = nullptr;   // the stream the ctx's last call enqueued on
-  bool last_stream_valid = false;
-  struct Retired {                // an arena outgrown while possibly in use (arena_alloc)
-    char *p;
-    std::vector<hipEvent_t> done;   // recorded on every stream the ctx has worked on
-  };
-  std::vector<Retired> retired;
-  std::vector<hipStream_t> streams;   // streams the ctx's work was enqueued on (note_stream)
   // dispatch: the defaults are the measured best; the environment knobs are
   // for tests (named in tests/test_gpu_parity.py) and diagnostics
   int roll_seg = 0;          // TVL1_ROLL_SEG: k_iterate_roll rows per segment (0 = auto)
@@ -156,8 +206,7 @@ struct tvl1_ctx {
                              // while other solves share it (longer segments than the other
                              // streaming launches take: a block's run-in is 3 K - 1 steps)
   // batch arena (tvl1_calc_batch): per logical plane, kBatchMax pairs' copies
-  char *barena = nullptr;
-  size_t barena_bytes = 0;
+  Block barena;
   int bW = 0, bH = 0, bL = 0, bn = 0;   // geometry it is laid out for
   int bws[TVL1_MAX_LEVELS] = {}, bhs[TVL1_MAX_LEVELS] = {};   // ... and its level sizes
   float *bI0s[TVL1_MAX_LEVELS] = {}, *bI1s[TVL1_MAX_LEVELS] = {};
@@ -180,23 +229,18 @@ struct tvl1_ctx {
                                         // block (occupancy probe only; with the LDS-staged
                                         // passes' 40 KiB, at most 120 KiB)
   int probe_wi_lds = 0;                 // TVL1_PROBE_WI_LDS: the same for k_warp_iter (< 64 KiB)
-  char *gather_scratch = nullptr;       // tvl1_gather_flow's offsets and values
-  size_t gather_bytes = 0;
+  Block gather_scratch;                 // tvl1_gather_flow's offsets and values
   int batch_small = 1;                  // TVL1_BATCH_SMALL=0: the coarsest level of a batch
                                         // streams like the others (no kb_small_level)
-  char *small_scratch = nullptr;        // kb_small_level's per-warp iteration counts
-  size_t small_bytes = 0;
-  float *map_scratch = nullptr;         // tvl1_postprocess_affine's staged map planes
-  size_t map_bytes = 0;
-  char *align_scratch = nullptr;        // tvl1_find_alignment's pyramid, keys, descriptors
-  size_t align_bytes = 0;
+  Block small_scratch;                  // kb_small_level's per-warp iteration counts
+  Block map_scratch;                    // tvl1_postprocess_affine's staged map planes
+  Block align_scratch;                  // tvl1_find_alignment's pyramid, keys, descriptors
   int4 *align_pat = nullptr;            // the rBRIEF pair pattern (device, set once)
-  char *shift_scratch = nullptr;        // tvl1_estimate_shift's pyramids, tables and records
-  size_t shift_bytes = 0;
-  char *seed_scratch = nullptr;         // tvl1_calc_batch_const_init / _auto_init: every pair's
-  size_t seed_bytes = 0;                // constants (then two planes for pairs solved alone)
-  char *count_scratch = nullptr;        // the counted utility calls' per-pair counters (zero_above, compose,
-  size_t count_bytes = 0;               // invert): one block, no solver scratch, sized once for a chunk of
+  Block shift_scratch;                  // tvl1_estimate_shift's pyramids, tables and records
+  Block seed_scratch;                   // tvl1_calc_batch_const_init / _auto_init: every pair's
+                                        // constants (then two planes for pairs solved alone)
+  Block count_scratch;                  // the counted utility calls' per-pair counters (zero_above, compose,
+                                        // invert): one block, no solver scratch, sized once for a chunk of
                                         // the largest record.  Shared safely: a counted call synchronises
                                         // its stream before it returns, and a ctx is used from one thread
   bool invert_window = true;            // TVL1_INVERT_WINDOW: k_invert_flow's LDS-window arm (the default:
@@ -204,50 +248,15 @@ struct tvl1_ctx {
   int bnblk = 0;                        // partials per pair
   int check = 0;             // TVL1_CHECK=1: synchronise + check after every launch (diagnostics)
 
-  // optional per-kernel-class HIP-event timing (tvl1_set_profiling)
+  // optional per-kernel-class HIP-event timing (tvl1_set_profiling).  A solve's marks are
+  // reset when it starts.  The slice-list and utility calls (tvl1_blend6_u8, tvl1_half_u8,
+  // tvl1_remap_flow_u8, run_chunks) run outside a solve, so their marks (class 2) wait in a
+  // pool of their own for the next solve's totals (sum_marks): at most kStackMarks of them; a
+  // caller that never solves loses the later ones, not memory.
   bool profiling = false;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
-  struct Mark {
-    int cls;
-    size_t a, b;
-    double bytes;      // SURVEY 8(d) algorithmic bytes
-    double hbm_bytes;  // compulsory bytes of this implementation
-  };
-  std::vector<Mark> marks;
-  // the same for the slice-list calls (tvl1_blend6_u8, tvl1_half_u8, tvl1_remap_flow_u8): they
-  // run outside a solve, so their marks wait here, with events of their own, for the next
-  // solve's totals (class 2)
-  std::vector<hipEvent_t> xev_pool;
-  size_t xev_used = 0;
-  std::vector<Mark> xmarks;
+  static constexpr size_t kStackMarks = 1024;
+  MarkPool prof{64, 0}, xprof{2, kStackMarks};
 };
-
-static size_t prof_begin(tvl1_ctx *c, hipStream_t st) {
-  if (!c->profiling) return 0;
-  if (c->ev_used + 2 > c->ev_pool.size()) {
-    for (int i = 0; i < 64; ++i) {
-      hipEvent_t e;
-      // timing-only events: no system-scope fence (cache writeback + invalidate) at each
-      // record, which slowed the kernel after it and inflated the per-launch times ~6 %
-      // against the rocprofv3 kernel trace (r3)
-      if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) break;
-      c->ev_pool.push_back(e);
-    }
-  }
-  if (c->ev_used + 2 > c->ev_pool.size()) return 0;
-  const size_t a = c->ev_used++;
-  (void)hipEventRecord(c->ev_pool[a], st);
-  return a + 1;  // 0 = not recording
-}
-
-static void prof_end(tvl1_ctx *c, hipStream_t st, size_t tok, int cls, double bytes,
-                     double hbm_bytes = -1.0) {
-  if (!c->profiling || tok == 0) return;
-  const size_t b = c->ev_used++;
-  (void)hipEventRecord(c->ev_pool[b], st);
-  c->marks.push_back({cls, tok - 1, b, bytes, hbm_bytes < 0 ? bytes : hbm_bytes});
-}
 
 static tvl1_status set_err(tvl1_ctx *c, tvl1_status st, const char *fmt, ...) {
   char buf[512];
@@ -268,6 +277,12 @@ static tvl1_status set_err(tvl1_ctx *c, tvl1_status st, const char *fmt, ...) {
     if (e_ != hipSuccess)                                                               \
       return set_err((ctx), TVL1_EHIP, "%s failed: %s (%s:%d)", #expr,                 \
                      hipGetErrorString(e_), __FILE__, __LINE__);                        \
+  } while (0)
+
+#define TVL1_TRY(expr)                 \
+  do {                                 \
+    tvl1_status r_ = (expr);           \
+    if (r_ != TVL1_OK) return r_;      \
   } while (0)
 
 static tvl1_status check_params(tvl1_ctx *c, const tvl1_params *p) {
@@ -301,131 +316,16 @@ static int math_of(const tvl1_params &p) {
   return p.gamma != 0.0 || exact_div ? kIEEE : p.fast_math;
 }
 
-// (Re)allocate one of the ctx's scratch arenas, zero-filled, for work on stream `use`.
-// The old allocation may still be read by work the ctx enqueued (tvl1_calc is
-// asynchronous).  It is retired, not freed at once: events recorded on the ctx's recent
-// streams (note_stream keeps the last 8) mark its last use, and reap_retired releases it
-// once they are done, or waits for the oldest when more than kRetiredMax are held, or at
-// tvl1_destroy.  What makes the release safe is hipFree itself: on ROCm it synchronises the
-// whole device before it frees, so a retired arena is never freed under a kernel that
-// still reads it, whatever stream that kernel is on.  The price is that a reap stalls every
-// other context's pairs in flight for that moment; it happens only when an arena was
-// outgrown (geometry growth, at most twice held), never in the steady state of a job whose
-// sizes repeat.  The arenas are only ever grown: a smaller layout re-lays the existing
-// allocation (ensure_geometry, ensure_batch), ordered across streams by order_streams.  The
-// work on `use` is ordered after the zero fill by an event, not by a host wait.  (The stream-ordered
-// allocator, hipMallocAsync / hipFreeAsync, would release in stream order too, but it
-// deadlocked against a concurrent hipStreamDestroy on this ROCm, so it is not used.)
-// Remember a stream the ctx enqueues work on, so a retired arena can be released once every
-// such stream has passed the point of its retirement.
-static void note_stream(tvl1_ctx *c, hipStream_t s) {
-  for (size_t i = 0; i < c->streams.size(); ++i)
-    if (c->streams[i] == s) {   // most recent last
-      c->streams.erase(c->streams.begin() + i);
-      break;
-    }
-  c->streams.push_back(s);
-  if (c->streams.size() > 8) c->streams.erase(c->streams.begin());
-}
-
-static void free_retired(tvl1_ctx::Retired &r) {
-  (void)hipFree(r.p);
-  for (hipEvent_t e : r.done) (void)hipEventDestroy(e);
-  r.done.clear();
-}
-
-// Release the retired arenas whose work has finished (every event done); with `wait`, the
-// oldest ones are waited for too until at most kRetiredMax remain.  A caller that alternates
-// geometries therefore holds a bounded number of old arenas.
-static constexpr size_t kRetiredMax = 2;
-static void reap_retired(tvl1_ctx *c, bool wait) {
-  size_t keep = 0;
-  for (size_t i = 0; i < c->retired.size(); ++i) {
-    tvl1_ctx::Retired &r = c->retired[i];
-    bool done = true;
-    const bool must = wait && c->retired.size() - i > kRetiredMax;
-    for (hipEvent_t e : r.done) {
-      if (must) (void)hipEventSynchronize(e);
-      else if (hipEventQuery(e) != hipSuccess) done = false;
-    }
-    (void)hipGetLastError();   // hipErrorNotReady is not an error
-    if (done) free_retired(r);
-    else c->retired[keep++] = r;
-  }
-  c->retired.resize(keep);
-}
-
-// A ctx's arenas are reused (and re-laid in place) by every call, so a call on a stream
-// other than the previous call's must not start before that stream's work on them is done
-// (a batch re-laid for a new geometry on stream B while stream A's kb_output still
-// reads the old layout).  One event record + stream wait per switch of streams; a ctx that
-// stays on one stream pays nothing.  A stream the caller has destroyed since has nothing
-// left on it: its record fails and is ignored.
-static void order_streams(tvl1_ctx *c, hipStream_t st) {
-  if (c->last_stream_valid && c->last_stream != st) {
-    if (hipEventRecord(c->ev_switch, c->last_stream) == hipSuccess)
-      (void)hipStreamWaitEvent(st, c->ev_switch, 0);
-    (void)hipGetLastError();
-  }
-  c->last_stream = st;
-  c->last_stream_valid = true;
-}
-
-static tvl1_status arena_alloc(tvl1_ctx *c, char **arena, size_t *have, size_t bytes,
-                               hipStream_t use) {
-  note_stream(c, use);
-  if (*arena) {
-    tvl1_ctx::Retired r{*arena, {}};
-    note_stream(c, c->own_stream);
-    for (hipStream_t s : c->streams) {
-      hipEvent_t e = nullptr;
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-        (void)hipGetLastError();
-        continue;
-      }
-      if (hipEventRecord(e, s) != hipSuccess) {   // a destroyed stream: nothing left on it
-        (void)hipGetLastError();
-        (void)hipEventDestroy(e);
-        continue;
-      }
-      r.done.push_back(e);
-    }
-    c->retired.push_back(r);
-    *arena = nullptr;
-    *have = 0;
-    reap_retired(c, true);
-  }
-  hipError_t e = hipMalloc((void **)arena, bytes);
-  if (e != hipSuccess && !c->retired.empty()) {
-    // out of memory with outgrown arenas held: release them (hipFree waits for the device;
-    // a rare path, better than failing) and try once more
-    (void)hipGetLastError();
-    for (auto &r : c->retired) free_retired(r);
-    c->retired.clear();
-    e = hipMalloc((void **)arena, bytes);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();   // not sticky: the caller may retry smaller
-    *arena = nullptr;
-    return set_err(c, TVL1_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  }
-  *have = bytes;
-  // zero once so pitch padding starts finite (hipMemsetAsync on the ctx's stream: a plain
-  // hipMemset runs on the legacy null stream, unordered with non-blocking streams)
-  HIP_TRY(c, hipMemsetAsync(*arena, 0, bytes, c->own_stream));
-  if (use != c->own_stream) {
-    HIP_TRY(c, hipEventRecord(c->ev_order, c->own_stream));
-    HIP_TRY(c, hipStreamWaitEvent(use, c->ev_order, 0));
-  }
-  return TVL1_OK;
+// Grow a block of the ctx (tvl1_arena.hpp); the reason of a failure goes to the ctx's error text.
+static tvl1_status reserve(tvl1_ctx *c, Block &b, size_t need, hipStream_t st, size_t floor = 0) {
+  const tvl1_status r = c->mem.reserve(b, need, st, floor);
+  return r == TVL1_OK ? r : set_err(c, r, "%s", c->mem.err);
 }
 
 // Carve the arena for a geometry; grows (never shrinks) the device allocation.  The
 // calls's work goes to stream st.
 static tvl1_status ensure_geometry(tvl1_ctx *c, int W, int H, hipStream_t st) {
-  order_streams(c, st);
-  note_stream(c, st);
-  if (!c->retired.empty()) reap_retired(c, false);
+  c->mem.enter(st);
   Geometry g;
   g.W = W;
   g.H = H;
@@ -451,12 +351,9 @@ static tvl1_status ensure_geometry(tvl1_ctx *c, int W, int H, hipStream_t st) {
   bytes += align_up((size_t)nblk * sizeof(double), 256);
   bytes += 4096;                            // alignment slack
 
-  if (bytes > c->arena_bytes) {
-    c->geo_valid = false;
-    const tvl1_status r = arena_alloc(c, &c->arena, &c->arena_bytes, bytes, st);
-    if (r != TVL1_OK) return r;
-  }
-  char *p = c->arena;
+  if (bytes > c->arena.bytes) c->geo_valid = false;
+  TVL1_TRY(reserve(c, c->arena, bytes, st));
+  char *p = c->arena.p;
   auto take = [&](size_t n) {
     char *r = p;
     p += align_up(n, 256);
@@ -514,12 +411,6 @@ static inline dim3 grid2(int w, int h, int z = 1) {
   return dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)z);
 }
 static const dim3 kBlk2(64, 4, 1);
-
-#define TVL1_TRY(expr)                 \
-  do {                                 \
-    tvl1_status r_ = (expr);           \
-    if (r_ != TVL1_OK) return r_;      \
-  } while (0)
 
 // ---- fills shared by the solve paths
 // IterArgs scalars of a level: its sizes, the solver's float parameters and where the residual
@@ -601,31 +492,25 @@ struct ClassTotals {
   double ms[4] = {}, bytes[4] = {}, hbm[4] = {};
   int64_t launches[4] = {};
 };
-static tvl1_status sum_marks(tvl1_ctx *c, ClassTotals &t) {
-  if (c->profiling && !c->xmarks.empty()) {   // slice-list calls since the last solve
-    for (const auto &m : c->xmarks) {
-      float ms = 0.f;
-      HIP_TRY(c, hipEventSynchronize(c->xev_pool[m.b]));
-      HIP_TRY(c, hipEventElapsedTime(&ms, c->xev_pool[m.a], c->xev_pool[m.b]));
-      t.ms[m.cls] += ms;
-      t.launches[m.cls] += 1;
-      t.bytes[m.cls] += m.bytes;
-      t.hbm[m.cls] += m.hbm_bytes;
-    }
-    c->xmarks.clear();
-    c->xev_used = 0;
-  }
-  if (!c->profiling || c->marks.empty()) return TVL1_OK;
-  HIP_TRY(c, hipEventSynchronize(c->ev_pool[c->marks.back().b]));
-  for (const auto &m : c->marks) {
+// each: wait for every mark's event (marks of several streams), not for the last one's only
+static tvl1_status add_marks(tvl1_ctx *c, const MarkPool &p, bool each, ClassTotals &t) {
+  if (!c->profiling || p.marks.empty()) return TVL1_OK;
+  if (!each) HIP_TRY(c, hipEventSynchronize(p.ev[p.marks.back().b]));
+  for (const auto &m : p.marks) {
     float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_pool[m.a], c->ev_pool[m.b]));
+    if (each) HIP_TRY(c, hipEventSynchronize(p.ev[m.b]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, p.ev[m.a], p.ev[m.b]));
     t.ms[m.cls] += ms;
     t.launches[m.cls] += 1;
     t.bytes[m.cls] += m.bytes;
     t.hbm[m.cls] += m.hbm_bytes;
   }
   return TVL1_OK;
+}
+static tvl1_status sum_marks(tvl1_ctx *c, ClassTotals &t) {
+  TVL1_TRY(add_marks(c, c->xprof, true, t));   // slice-list calls since the last solve
+  if (c->profiling) c->xprof.reset();
+  return add_marks(c, c->prof, false, t);
 }
 static void put_class_totals(tvl1_stats *s, const ClassTotals &t) {
   for (int k = 0; k < 4; ++k) {
@@ -900,7 +785,7 @@ static tvl1_status gather(const Level &lv, int uset, int cbuf, int wp) {
   tvl1_ctx *c = lv.c;
   hipStream_t st = lv.st;
   const int s = lv.s, lw = lv.lw, lh = lv.lh, P = lv.P;
-  size_t t0 = prof_begin(c, st);
+  size_t t0 = c->prof.begin(c->profiling, st);
   if (!lv.roll_ok) {
     const int tx = (lw + kWarpTW - 1) / kWarpTW, ty = (lh + kWarpTH - 1) / kWarpTH;
 #define WARP_IMG(FM)                                                                           \
@@ -931,7 +816,7 @@ static tvl1_status gather(const Level &lv, int uset, int cbuf, int wp) {
 #undef WARP_RING
   }
   // algorithmic: 40 B/px per warp; compulsory here ~28 B/px (I1 x 1 + 2M/64)
-  prof_end(c, st, t0, 1, (double)lw * lh * 40.0, (double)lw * lh * 28.0);
+  c->prof.end(st, t0, 1, (double)lw * lh * 40.0, (double)lw * lh * 28.0);
   DIAG(c, st, "warp kernel", s, wp, -1);
   return TVL1_OK;
 }
@@ -946,7 +831,7 @@ static tvl1_status upsample(const Level &lv, int uset) {
   const float fxu = (float)(1.0 / ((double)dw / lw));
   const float fyu = (float)(1.0 / ((double)dh / lh));
   const float upmul = (float)(1.0 / c->prm.scale_step);
-  size_t t0 = prof_begin(c, st);
+  size_t t0 = c->prof.begin(c->profiling, st);
   if (contracts(lv.math))
     hipLaunchKernelGGL(k_upsample<true>, grid2(dw, dh, lv.gam ? 3 : 2), kBlk2, 0, st, c->U[uset][0],
                        c->U[uset][1], c->U[uset][2], lw, lh, g.ps[s], c->U[uset ^ 1][0],
@@ -955,7 +840,7 @@ static tvl1_status upsample(const Level &lv, int uset) {
     hipLaunchKernelGGL(k_upsample<false>, grid2(dw, dh, lv.gam ? 3 : 2), kBlk2, 0, st, c->U[uset][0],
                        c->U[uset][1], c->U[uset][2], lw, lh, g.ps[s], c->U[uset ^ 1][0],
                        c->U[uset ^ 1][1], c->U[uset ^ 1][2], dw, dh, g.ps[s - 1], fxu, fyu, upmul);
-  prof_end(c, st, t0, 2, (double)lw * lh * 8.0 + (double)dw * dh * 8.0);
+  c->prof.end(st, t0, 2, (double)lw * lh * 8.0 + (double)dw * dh * 8.0);
   DIAG(c, st, "k_upsample", s, -1, -1);
   return TVL1_OK;
 }
@@ -1164,7 +1049,7 @@ static tvl1_status launch_pass(const Level &lv, const PassReq &p, int wp, int n,
   a.p_zero = p.p_zero ? 1 : 0;
   a.gate = p.gated ? c->gate : nullptr;
   a.gate_seq = p.gseq;
-  const size_t tkp = prof_begin(c, lv.st);
+  const size_t tkp = c->prof.begin(c->profiling, lv.st);
   const double Nl = (double)lv.lw * lv.lh;
   double hbm = 0.0;
   int blocks;
@@ -1183,7 +1068,7 @@ static tvl1_status launch_pass(const Level &lv, const PassReq &p, int wp, int n,
   if (blocks < 0) return TVL1_EHIP;
   // algorithmic: 64 B/px per executed iteration (+ 40 B/px for a fused
   // warpBackward)
-  prof_end(c, lv.st, tkp, 0, Nl * 64.0 * p.k + (p.witer ? Nl * 40.0 : 0.0), hbm);
+  c->prof.end(lv.st, tkp, 0, Nl * 64.0 * p.k + (p.witer ? Nl * 40.0 : 0.0), hbm);
   DIAG(c, lv.st, "iteration pass", lv.s, wp, n);
   blocks_out = blocks;
   return TVL1_OK;
@@ -1233,10 +1118,10 @@ struct LevelOps {
     return launch_check(lv.c, lv.st, q.blocks, gt, seq, q.first);
   }
   tvl1_status wait(unsigned long long seq, double *e) { return wait_check(lv.c, lv.st, seq, e); }
-  Mark mark() const { return Mark{lv.c->marks.size(), lv.c->ev_used, lv.c->check_seq}; }
+  Mark mark() const { return Mark{lv.c->prof.marks.size(), lv.c->prof.used, lv.c->check_seq}; }
   void rollback(const Mark &m) {
-    lv.c->marks.resize(m.marks);
-    lv.c->ev_used = m.ev_used;
+    lv.c->prof.marks.resize(m.marks);
+    lv.c->prof.used = m.ev_used;
     lv.c->check_seq = m.check_seq;
   }
   // speculates only a solve alone on its device (TVL1_SPEC=2: always)
@@ -1253,7 +1138,7 @@ struct LevelOps {
 // [A.1] convertTo + [A.2] pyramid, kernel step = float(1/scaleStep)
 static tvl1_status build_pyramid(tvl1_ctx *c, const Frames &in, int W, int H, hipStream_t st) {
   const Geometry &g = c->geo;
-  const size_t tk = prof_begin(c, st);
+  const size_t tk = c->prof.begin(c->profiling, st);
   convert_frames(c, in, W, H, st);
   const float fdown = (float)(1.0 / c->prm.scale_step);
   const bool contract_pyr = contracts(math_of(c->prm));
@@ -1269,7 +1154,7 @@ static tvl1_status build_pyramid(tvl1_ctx *c, const Frames &in, int W, int H, hi
   }
   double b = (double)W * H * (2 + 8);
   for (int s = 1; s < g.L; ++s) b += (double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8;
-  prof_end(c, st, tk, 2, b);
+  c->prof.end(st, tk, 2, b);
   HIP_TRY(c, hipGetLastError());
   return TVL1_OK;
 }
@@ -1295,7 +1180,7 @@ static tvl1_status initial_flow(tvl1_ctx *c, const Seed *seed, int W, int H, hip
   const float fdown = (float)(1.0 / c->prm.scale_step);
   const float fmul = (float)c->prm.scale_step;
   const bool contract_pyr = contracts(math_of(c->prm));
-  const size_t tk = prof_begin(c, st);
+  const size_t tk = c->prof.begin(c->profiling, st);
   double b = 0.0;
   if (L == 1) {
     hipLaunchKernelGGL(kb_flow_copy, grid2(W, H, 2), kBlk2, 0, st, seed->u0, seed->v0,
@@ -1317,7 +1202,7 @@ static tvl1_status initial_flow(tvl1_ctx *c, const Seed *seed, int W, int H, hip
                          g.hs[s], g.ps[s], fdown, fdown, fmul);
     b += (double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8;
   }
-  prof_end(c, st, tk, 2, b);
+  c->prof.end(st, tk, 2, b);
   if (gam)
     HIP_TRY(c, hipMemsetAsync(c->U[ui][2], 0, (size_t)g.ps[L - 1] * g.hs[L - 1] * sizeof(float), st));
   HIP_TRY(c, hipGetLastError());
@@ -1338,10 +1223,7 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
   const int L = g.L;
   const bool gam = g.gamma;
   const bool median = prm.median_filtering > 1;
-  if (c->profiling) {
-    c->ev_used = 0;
-    c->marks.clear();
-  }
+  if (c->profiling) c->prof.reset();
 
   TVL1_TRY(build_pyramid(c, in, W, H, st));
   WalkState ws{0, 0, 0, 50.0};   // the buffer sets in use (u, p, constants), and w0_hint
@@ -1404,10 +1286,10 @@ static tvl1_status solve(tvl1_ctx *c, const Frames &in, const Seed *seed, int W,
     TVL1_TRY(upsample(lv, ws.ui));  // zoom the flow to level s-1, scale by 1/scaleStep
     ws.ui ^= 1;
   }
-  const size_t tk = prof_begin(c, st);
+  const size_t tk = c->prof.begin(c->profiling, st);
   hipLaunchKernelGGL(k_output, grid2(W, H), kBlk2, 0, st, c->U[ws.ui][0], c->U[ws.ui][1], W, H,
                      g.ps[0], u, v, fpitch);
-  prof_end(c, st, tk, 2, (double)W * H * 16.0);
+  c->prof.end(st, tk, 2, (double)W * H * 16.0);
   HIP_TRY(c, hipGetLastError());
 
   ClassTotals tot;
@@ -1430,7 +1312,7 @@ static tvl1_status ensure_batch(tvl1_ctx *c, int W, int H, int n, hipStream_t st
   const Geometry &g = c->geo;   // pyramid sizes of (W, H) (ensure_geometry ran)
   // reuse only for the same level sizes: a new scaleStep with the same level count changes
   // every level's plane stride (c->bips), and the kernels would write past each pair's slot
-  if (c->barena && c->bW == W && c->bH == H && c->bL == g.L && c->bn >= n &&
+  if (c->barena.p && c->bW == W && c->bH == H && c->bL == g.L && c->bn >= n &&
       !memcmp(c->bws, g.ws, sizeof(int) * g.L) && !memcmp(c->bhs, g.hs, sizeof(int) * g.L))
     return TVL1_OK;
   const size_t P0 = (size_t)g.ps[0];
@@ -1447,11 +1329,8 @@ static tvl1_status ensure_batch(tvl1_ctx *c, int W, int H, int n, hipStream_t st
   c->bW = c->bH = c->bL = c->bn = 0;
   // a layout that fits re-lays the existing arena (stream-ordered like ensure_geometry's):
   // only growth allocates, so alternating batch geometries hold one arena
-  if (bytes > c->barena_bytes) {
-    const tvl1_status r = arena_alloc(c, &c->barena, &c->barena_bytes, bytes, st);
-    if (r != TVL1_OK) return r;   // TVL1_ENOMEM: the caller retries a smaller chunk
-  }
-  char *p = c->barena;
+  TVL1_TRY(reserve(c, c->barena, bytes, st));   // TVL1_ENOMEM: the caller retries a smaller chunk
+  char *p = c->barena.p;
   auto take = [&](size_t nbytes) {
     char *r = p;
     p += align_up(nbytes, 256);
@@ -1531,7 +1410,7 @@ static tvl1_status batch_initial_flow(tvl1_ctx *c, int n, const Seed *seed, int 
   const float fdown = (float)(1.0 / c->prm.scale_step);
   const float fmul = (float)c->prm.scale_step;
   const bool contract = contracts(math_of(c->prm));
-  const size_t tkf = prof_begin(c, st);
+  const size_t tkf = c->prof.begin(c->profiling, st);
   double fb = 0.0;
   if (L == 1 && seed->cst) {
     hipLaunchKernelGGL(kb_flow_fill, grid2(W, H, 2 * n), kBlk2, 0, st, seed->cst, c->bU[0][0],
@@ -1571,7 +1450,7 @@ static tvl1_status batch_initial_flow(tvl1_ctx *c, int n, const Seed *seed, int 
 #undef KB_FLOW
     fb += (double)n * ((double)g.ws[s] * g.hs[s] * 8 + (double)g.ws[s - 1] * g.hs[s - 1] * 8);
   }
-  prof_end(c, st, tkf, 2, fb);
+  c->prof.end(st, tkf, 2, fb);
   return TVL1_OK;
 }
 
@@ -1586,8 +1465,7 @@ static tvl1_status batch_small_level(const BatchLevel &bl, const BatchSel &all, 
   const tvl1_params &prm = c->prm;
   const int n = bl.n, lw = bl.lw, lh = bl.lh;
   const size_t need = (size_t)n * (prm.warps + 1) * sizeof(int);
-  if (need > c->small_bytes)
-    TVL1_TRY(arena_alloc(c, &c->small_scratch, &c->small_bytes, std::max<size_t>(need, 64 << 10), st));
+  TVL1_TRY(reserve(c, c->small_scratch, need, st, 64 << 10));
   BatchSmall sm{};
   sm.I0 = c->bI0s[bl.s];
   sm.I1 = c->bI1s[bl.s];
@@ -1603,10 +1481,10 @@ static tvl1_status batch_small_level(const BatchLevel &bl, const BatchSel &all, 
   sm.eps_pos = prm.epsilon > 0;
   sm.thr = scaledEps;
   sm.it = bl.it;
-  sm.warp_iters = reinterpret_cast<int *>(c->small_scratch);
+  sm.warp_iters = c->small_scratch.as<int>();
   sm.checks = sm.warp_iters + (size_t)n * prm.warps;
   sm.sel = all;
-  const size_t tks = prof_begin(c, st);
+  const size_t tks = c->prof.begin(c->profiling, st);
 #define KB_SMALL(FM)                                                                               \
   if (seeded)                                                                                     \
     hipLaunchKernelGGL((kb_small_level<FM, true>), dim3(n), dim3(64 * ((lw + 63) / 64)), 0, st, sm); \
@@ -1616,13 +1494,13 @@ static tvl1_status batch_small_level(const BatchLevel &bl, const BatchSel &all, 
 #undef KB_SMALL
   HIP_TRY(c, hipGetLastError());
   hw.resize((size_t)n * (prm.warps + 1));
-  HIP_TRY(c, hipMemcpyAsync(hw.data(), c->small_scratch, need, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(hw.data(), c->small_scratch.p, need, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   int64_t it_sum = 0;
   for (size_t i = 0; i < (size_t)n * prm.warps; ++i) it_sum += hw[i];
   // its own class (3): SURVEY 8(d)'s bytes of every iteration and warp it ran, but from HBM
   // it only reads I0, I1 and writes u once, so it would skew class 0's HBM roofline
-  prof_end(c, st, tks, 3, (double)lw * lh * (64.0 * it_sum + 40.0 * n * prm.warps),
+  c->prof.end(st, tks, 3, (double)lw * lh * (64.0 * it_sum + 40.0 * n * prm.warps),
            (double)lw * lh * 16.0 * n);
   return TVL1_OK;
 }
@@ -1655,7 +1533,7 @@ static int launch_batch_warp_iter(const BatchLevel &bl, const BatchSel &sel, int
   wi.partials = c->bpartials;
   wi.nblk = sp.waves;
   wi.sel = sel;
-  const size_t tkw = prof_begin(c, st);
+  const size_t tkw = c->prof.begin(c->profiling, st);
 #define KB_WITER(FM)                                                                             \
   if (c->wi_nc == 2)                                                                            \
     hipLaunchKernelGGL((kb_warp_iter<6, FM, 2>), dim3(wi.w.ra.waves, n), dim3(256), 0, st, wi); \
@@ -1667,7 +1545,7 @@ static int launch_batch_warp_iter(const BatchLevel &bl, const BatchSel &sel, int
     const double Nl = (double)bl.lw * bl.lh;
     int nz = 0;   // pairs whose p is zero (a level's first warp): p not loaded
     for (int b = 0; b < n; ++b) nz += sel.pzero.test(b) ? 1 : 0;
-    prof_end(c, st, tkw, 0, (double)n * Nl * (64.0 * 2 + 40.0),
+    c->prof.end(st, tkw, 0, (double)n * Nl * (64.0 * 2 + 40.0),
              batch_warp_iter_hbm(sp, bl.lh, wi_ww<6, 128>(), Nl, n, nz, nstore));
   }
   return sp.waves;
@@ -1693,12 +1571,12 @@ static void launch_batch_ring(const BatchLevel &bl, const BatchSel &sel) {
   br.ips = c->bips[bl.s];
   br.ps = bl.ps;
   br.sel = sel;
-  const size_t tkr = prof_begin(c, st);
+  const size_t tkr = c->prof.begin(c->profiling, st);
 #define KB_RING(FM) \
   hipLaunchKernelGGL((kb_warp_ring<6, 2, FM>), dim3(br.wa.waves, sel.n), dim3(128), 0, st, br);
   MATH_SWITCH(bl.math, KB_RING)
 #undef KB_RING
-  prof_end(c, st, tkr, 1, (double)sel.n * lw * lh * 40.0, (double)sel.n * lw * lh * 28.0);
+  c->prof.end(st, tkr, 1, (double)sel.n * lw * lh * 40.0, (double)sel.n * lw * lh * 28.0);
 }
 
 // One pass group: K iterations for the pairs of sel (kb_iterate_roll: wavefront pipelines,
@@ -1731,7 +1609,7 @@ static int launch_batch_roll(const BatchLevel &bl, int K, const BatchSel &sel) {
   br.nblk = c->bnblk;
   br.sel = sel;
   const dim3 grid((br.ra.waves + 3) / 4, sel.n);
-  const size_t tkp = prof_begin(c, st);
+  const size_t tkp = c->prof.begin(c->profiling, st);
 #define KB_ROLL_M(FM)                                                                       \
   if (px == 1)                                                                            \
     hipLaunchKernelGGL((kb_iterate_roll<KK, 1, FM>), grid, dim3(256), 0, st, br);         \
@@ -1754,7 +1632,7 @@ static int launch_batch_roll(const BatchLevel &bl, int K, const BatchSel &sel) {
     const double Nl = (double)lw * lh;
     int nz = 0;
     for (int j = 0; j < sel.n; ++j) nz += sel.pzero.test(sel.idx[j]) ? 1 : 0;
-    prof_end(c, st, tkp, 0, (double)sel.n * Nl * 64.0 * K, batch_roll_hbm(sp, lh, K, px, Nl, sel.n, nz));
+    c->prof.end(st, tkp, 0, (double)sel.n * Nl * 64.0 * K, batch_roll_hbm(sp, lh, K, px, Nl, sel.n, nz));
   }
   return sp.waves;
 }
@@ -1865,10 +1743,7 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
   // shared share measured neutral here: 2925 / 2901 against 2919 / 2928 strip solves/s,
   // profiles/r3/ab_batch_fill.txt)
   const SolveCount active(c->device);
-  if (c->profiling) {   // per-class HIP events of this chunk's launches (shared by its pairs)
-    c->ev_used = 0;
-    c->marks.clear();
-  }
+  if (c->profiling) c->prof.reset();   // per-class HIP events of this chunk's launches (shared by its pairs)
 
   batch_pyramid(c, n, I0, pitch0, stride0, I1, pitch1, stride1, W, H, st);
   TVL1_TRY(batch_initial_flow(c, n, seed, W, H, st));
@@ -1950,7 +1825,7 @@ static tvl1_status solve_batch_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size
   // launch serves all its pairs; bytes are summed over them)
   ClassTotals tot;
   TVL1_TRY(sum_marks(c, tot));
-  if (stats && c->profiling && !c->marks.empty())
+  if (stats && c->profiling && !c->prof.marks.empty())
     for (int b = 0; b < n; ++b) put_class_totals(&stats[b], tot);
   return TVL1_OK;
 }
@@ -2207,7 +2082,7 @@ tvl1_status tvl1_create(tvl1_ctx **out, int device, const tvl1_params *params) {
   if (const char *m = getenv("TVL1_FILL")) c->fill = std::max(10, atoi(m));
   if (const char *m = getenv("TVL1_FILL_SHARED")) c->fill_shared = std::max(10, atoi(m));
   if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
+      hipStreamCreateWithFlags(&c->mem.own, hipStreamNonBlocking) != hipSuccess ||
       hipHostMalloc((void **)&c->pinned, sizeof(double) * (8 + kBatchMax),
                     hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
       hipHostGetDevicePointer((void **)&c->pinned_dev, c->pinned, 0) != hipSuccess ||
@@ -2215,8 +2090,7 @@ tvl1_status tvl1_create(tvl1_ctx **out, int device, const tvl1_params *params) {
       hipEventCreateWithFlags(&c->ev_check[1], hipEventDisableTiming) != hipSuccess ||
       hipMalloc((void **)&c->gate, 256) != hipSuccess ||
       hipMemset(c->gate, 0, 256) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_switch, hipEventDisableTiming) != hipSuccess) {
+      !c->mem.init()) {
     delete c;
     return set_err(nullptr, TVL1_EHIP, "HIP initialisation failed on device %d", device);
   }
@@ -2418,7 +2292,7 @@ static tvl1_status calc_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0, size_t 
     per_pair += (((W + 55) / 56) * ((H + 23) / 24) + 64) * sizeof(double);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) {
-      const double avail = 0.5 * (double)free_b + (double)c->barena_bytes;
+      const double avail = 0.5 * (double)free_b + (double)c->barena.bytes;
       chunk = (int)std::max(1.0, std::min((double)chunk, avail / per_pair));
     }
   }
@@ -2516,7 +2390,7 @@ tvl1_status tvl1_find_alignment(tvl1_ctx *c, const uint8_t *frame1, size_t pitch
   }
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  order_streams(c, st);
+  c->mem.enter(st);
   {
     const tvl1_status r = ensure_pattern(c);
     if (r != TVL1_OK) return r;
@@ -2526,11 +2400,7 @@ tvl1_status tvl1_find_alignment(tvl1_ctx *c, const uint8_t *frame1, size_t pitch
   // one per-keypoint capacity for both frames (the quota sum can exceed nfeatures)
   const int kcap = std::max(g1.kcap, g0.kcap);
   const AlignCarve a1 = align_carve(g1, blur, kcap), a0 = align_carve(g0, blur, kcap);
-  const size_t need = std::max(a1.bytes, a0.bytes);
-  if (need > c->align_bytes) {
-    const tvl1_status r = arena_alloc(c, &c->align_scratch, &c->align_bytes, need, st);
-    if (r != TVL1_OK) return r;
-  }
+  TVL1_TRY(reserve(c, c->align_scratch, std::max(a1.bytes, a0.bytes), st));
   static const bool timing = getenv("TVL1_ALIGN_TIMING") != nullptr;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -2538,10 +2408,10 @@ tvl1_status tvl1_find_alignment(tvl1_ctx *c, const uint8_t *frame1, size_t pitch
   // query = frame1, train = frame0 (find_alignment(frame1_GPU, frame0_GPU)); the two frames
   // share the scratch's pyramid and keys and keep their descriptors apart
   OrbSet q, t;
-  const AlignPtrs cv = align_ptrs(c->align_scratch, a1);
+  const AlignPtrs cv = align_ptrs(c->align_scratch.p, a1);
   tvl1_status s = orb_detect(c, frame1, pitch1, g1, *ap, cv, cv.desc[0], q, st);
   const auto t1 = now();
-  const AlignPtrs cv0 = align_ptrs(c->align_scratch, a0);
+  const AlignPtrs cv0 = align_ptrs(c->align_scratch.p, a0);
   if (s == TVL1_OK) s = orb_detect(c, frame0, pitch0, g0, *ap, cv0, cv0.desc[1], t, st);
   const auto t2 = now();
   if (s != TVL1_OK) return s;
@@ -2610,7 +2480,7 @@ tvl1_status tvl1_orb_detect(tvl1_ctx *c, const uint8_t *frame, size_t pitch, int
   }
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  order_streams(c, st);
+  c->mem.enter(st);
   {
     const tvl1_status r = ensure_pattern(c);
     if (r != TVL1_OK) return r;
@@ -2618,12 +2488,8 @@ tvl1_status tvl1_orb_detect(tvl1_ctx *c, const uint8_t *frame, size_t pitch, int
   const OrbGeom g = orb_geom(w, h, *ap);
   const bool blur = ap->blur_for_descriptor != 0;
   const AlignCarve ac = align_carve(g, blur, g.kcap);
-  const size_t need = ac.bytes;
-  if (need > c->align_bytes) {
-    const tvl1_status r = arena_alloc(c, &c->align_scratch, &c->align_bytes, need, st);
-    if (r != TVL1_OK) return r;
-  }
-  const AlignPtrs cv = align_ptrs(c->align_scratch, ac);
+  TVL1_TRY(reserve(c, c->align_scratch, ac.bytes, st));
+  const AlignPtrs cv = align_ptrs(c->align_scratch.p, ac);
   OrbSet q;
   {
     const tvl1_status r = orb_detect(c, frame, pitch, g, *ap, cv, cv.desc[0], q, st, true);
@@ -2656,7 +2522,7 @@ tvl1_status tvl1_match_knn2(tvl1_ctx *c, const uint8_t *query, int32_t nq, const
   if (nq == 0) return TVL1_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  order_streams(c, st);
+  c->mem.enter(st);
   const MatchPlan mp = match_plan(nt);
   const int nseg = mp.nseg, seg = mp.seg;
   // scratch: query and train descriptors, the per-segment top-2, the merged top-2
@@ -2665,11 +2531,8 @@ tvl1_status tvl1_match_knn2(tvl1_ctx *c, const uint8_t *query, int32_t nq, const
   const size_t ob = op + align_up((size_t)nq * nseg * sizeof(Top2), 256);
   const size_t od = ob + align_up((size_t)nq * sizeof(int2), 256);
   const size_t need = od + align_up((size_t)nq * sizeof(int2), 256);
-  if (need > c->align_bytes) {
-    const tvl1_status r = arena_alloc(c, &c->align_scratch, &c->align_bytes, need, st);
-    if (r != TVL1_OK) return r;
-  }
-  char *b = c->align_scratch;
+  TVL1_TRY(reserve(c, c->align_scratch, need, st));
+  char *b = c->align_scratch.p;
   uint32_t *dq = (uint32_t *)(b + oq), *dt = (uint32_t *)(b + ot);
   Top2 *part = (Top2 *)(b + op);
   int2 *best = (int2 *)(b + ob), *dd = (int2 *)(b + od);
@@ -2707,15 +2570,9 @@ tvl1_status tvl1_postprocess_affine(tvl1_ctx *c, float *u, float *v, size_t fp, 
   if (W <= 0 || H <= 0) return set_err(c, TVL1_ESIZE, "bad size");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  order_streams(c, st);
-  const size_t need = 2 * (size_t)W * H * sizeof(float);
-  if (need > c->map_bytes) {
-    char *m = reinterpret_cast<char *>(c->map_scratch);
-    const tvl1_status r = arena_alloc(c, &m, &c->map_bytes, need, st);
-    c->map_scratch = reinterpret_cast<float *>(m);
-    if (r != TVL1_OK) return r;
-  }
-  float *m1 = c->map_scratch, *m2 = c->map_scratch + (size_t)W * H;
+  c->mem.enter(st);
+  TVL1_TRY(reserve(c, c->map_scratch, 2 * (size_t)W * H * sizeof(float), st));
+  float *m1 = c->map_scratch.as<float>(), *m2 = m1 + (size_t)W * H;
   Affine iM;
   affine_inverse(affine, iM);
   hipLaunchKernelGGL(ka_map_stage, grid2(W, H), kBlk2, 0, st, u, v, fp, W, H, m1, m2);
@@ -2726,28 +2583,7 @@ tvl1_status tvl1_postprocess_affine(tvl1_ctx *c, float *u, float *v, size_t fp, 
 }
 
 // ---- Average-flow alignment of a slice list (added under ABI 9; kernels in tvl1_stack.hpp) ----
-// Profiling marks of these calls (class 2): kept apart from a solve's, which are reset when
-// the solve starts, and added to the next solve's totals (sum_marks).  At most kStackMarks
-// wait; a caller that never solves loses the later ones, not memory.
-static constexpr size_t kStackMarks = 1024;
-static size_t xprof_begin(tvl1_ctx *c, hipStream_t st) {
-  if (!c->profiling || c->xmarks.size() >= kStackMarks) return 0;
-  while (c->xev_used + 2 > c->xev_pool.size()) {
-    hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return 0;
-    c->xev_pool.push_back(e);
-  }
-  const size_t a = c->xev_used++;
-  (void)hipEventRecord(c->xev_pool[a], st);
-  return a + 1;
-}
-static void xprof_end(tvl1_ctx *c, hipStream_t st, size_t tok, double bytes) {
-  if (tok == 0) return;
-  const size_t b = c->xev_used++;
-  (void)hipEventRecord(c->xev_pool[b], st);
-  c->xmarks.push_back({2, tok - 1, b, bytes, bytes});
-}
-
+// Profiling marks of these calls: class 2, in the ctx's xprof pool.
 static inline dim3 grid_lanes(int w, int h, int px) {
   return dim3(((w + px - 1) / px + 63) / 64, (h + 3) / 4, 1);
 }
@@ -2773,9 +2609,9 @@ tvl1_status tvl1_blend6_u8(tvl1_ctx *c, const uint8_t *const frames[6], const si
   if (dp < (size_t)W) return set_err(c, TVL1_EINVAL, "dst pitch below the row size");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  const size_t tok = xprof_begin(c, st);
+  const size_t tok = c->xprof.begin(c->profiling, st);
   hipLaunchKernelGGL(k_blend6_u8, grid_lanes(W, H, kStackPx), kBlk2, 0, st, a, W, H, dst, dp);
-  xprof_end(c, st, tok, 7.0 * W * H);
+  c->xprof.end(st, tok, 2,7.0 * W * H);
   HIP_TRY(c, hipGetLastError());
   return TVL1_OK;
 }
@@ -2789,10 +2625,10 @@ tvl1_status tvl1_half_u8(tvl1_ctx *c, const uint8_t *src, size_t sp, int32_t W, 
   if (sp < (size_t)W || dp < (size_t)(W / 2)) return set_err(c, TVL1_EINVAL, "pitch below the row size");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  const size_t tok = xprof_begin(c, st);
+  const size_t tok = c->xprof.begin(c->profiling, st);
   hipLaunchKernelGGL(k_half_u8, grid_lanes(W / 2, H / 2, kStackPx), kBlk2, 0, st, src, sp, W / 2,
                      H / 2, dst, dp);
-  xprof_end(c, st, tok, 1.25 * W * H);
+  c->xprof.end(st, tok, 2,1.25 * W * H);
   HIP_TRY(c, hipGetLastError());
   return TVL1_OK;
 }
@@ -2824,9 +2660,9 @@ tvl1_status tvl1_remap_flow_u8(tvl1_ctx *c, const uint8_t *frame, size_t pitch, 
   a.u = u, a.v = v, a.fpitch = fpitch / sizeof(float), a.fw = fw, a.fh = fh;
   a.gain = gain, a.scale_x = (double)fw / W, a.scale_y = (double)fh / H;
   a.border = border, a.dst = dst, a.dpitch = dp, a.CW = CW, a.CH = CH;
-  const size_t tok = xprof_begin(c, st);
+  const size_t tok = c->xprof.begin(c->profiling, st);
   hipLaunchKernelGGL(k_remap_flow_u8, grid_lanes(CW, CH, kRemapPx), kBlk2, 0, st, a);
-  xprof_end(c, st, tok, (double)W * H + (double)CW * CH + 8.0 * fw * fh);
+  c->xprof.end(st, tok, 2,(double)W * H + (double)CW * CH + 8.0 * fw * fh);
   HIP_TRY(c, hipGetLastError());
   return TVL1_OK;
 }
@@ -2875,13 +2711,6 @@ static tvl1_status check_shift_frames(tvl1_ctx *c, const uint8_t *I0, size_t p0,
   return TVL1_OK;
 }
 
-static tvl1_status ensure_shift_scratch(tvl1_ctx *c, size_t need, hipStream_t st) {
-  order_streams(c, st);
-  if (!c->retired.empty()) reap_retired(c, false);
-  if (need <= c->shift_bytes) return TVL1_OK;
-  return arena_alloc(c, &c->shift_scratch, &c->shift_bytes, std::max<size_t>(need, 64 << 10), st);
-}
-
 tvl1_status tvl1_sad_shifts_u8(tvl1_ctx *c, const uint8_t *I0, size_t p0, const uint8_t *I1, size_t p1,
                                int32_t w, int32_t h, int32_t cx, int32_t cy, int32_t radius,
                                uint64_t *sad, void *stream) {
@@ -2891,8 +2720,9 @@ tvl1_status tvl1_sad_shifts_u8(tvl1_ctx *c, const uint8_t *I0, size_t p0, const 
     return set_err(c, TVL1_EINVAL, "radius must be in 1..4 (got %d)", radius);
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  TVL1_TRY(ensure_shift_scratch(c, kShiftSlots * sizeof(uint64_t), st));
-  unsigned long long *table = reinterpret_cast<unsigned long long *>(c->shift_scratch);
+  c->mem.enter(st);
+  TVL1_TRY(reserve(c, c->shift_scratch, kShiftSlots * sizeof(uint64_t), st, 64 << 10));
+  unsigned long long *table = c->shift_scratch.as<unsigned long long>();
   HIP_TRY(c, hipMemsetAsync(table, 0, kShiftSlots * sizeof(uint64_t), st));
   // a centre further out than the frame has no overlap at any of its shifts; so has this one
   ShiftSadArgs a{I0, I1, p0, p1, 0, 0, w, h, nullptr, std::max(-(w + 8), std::min(w + 8, cx)),
@@ -2924,8 +2754,8 @@ static tvl1_status shift_chunk(tvl1_ctx *c, int n, const uint8_t *I0, size_t p0,
   const size_t tab_b = align_up((size_t)(L + 1) * n * kShiftSlots * sizeof(uint64_t), 256);
   const size_t base_b = align_up((size_t)(L + 1) * n * sizeof(int2), 256);
   const size_t rec_b = align_up((size_t)n * sizeof(tvl1_shift), 256);
-  TVL1_TRY(ensure_shift_scratch(c, tab_b + base_b + rec_b + one * (size_t)(n0 + n1), st));
-  char *p = c->shift_scratch;
+  TVL1_TRY(reserve(c, c->shift_scratch, tab_b + base_b + rec_b + one * (size_t)(n0 + n1), st, 64 << 10));
+  char *p = c->shift_scratch.p;
   unsigned long long *tables = reinterpret_cast<unsigned long long *>(p);
   int2 *bases = reinterpret_cast<int2 *>(p + tab_b);
   tvl1_shift *recs = reinterpret_cast<tvl1_shift *>(p + tab_b + base_b);
@@ -3006,6 +2836,7 @@ tvl1_status tvl1_estimate_shift_batch(tvl1_ctx *c, int32_t n, const uint8_t *I0,
   if (s != TVL1_OK) return s;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
+  c->mem.enter(st);
   TVL1_TRY(shift_chunks(c, n, I0, p0, s0, I1, p1, s1, w, h, R, out, nullptr, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   return TVL1_OK;
@@ -3033,17 +2864,15 @@ static tvl1_status calc_batch_const(tvl1_ctx *c, int32_t n, const uint8_t *I0, s
   // pairs solved one by one (gamma != 0) take their constant as planes, one pair's at a time
   const size_t cst_b = align_up((size_t)2 * n * sizeof(float), 256);
   const size_t plane_b = batch_chunk_max(c, H) > 0 ? 0 : align_up((size_t)W * H * sizeof(float), 256);
-  if (cst_b + 2 * plane_b > c->seed_bytes)
-    TVL1_TRY(arena_alloc(c, &c->seed_scratch, &c->seed_bytes,
-                         std::max<size_t>(cst_b + 2 * plane_b, 64 << 10), st));
-  float *cst = reinterpret_cast<float *>(c->seed_scratch);
+  TVL1_TRY(reserve(c, c->seed_scratch, cst_b + 2 * plane_b, st, 64 << 10));
+  float *cst = c->seed_scratch.as<float>();
   if (seed_xy)
     HIP_TRY(c, hipMemcpyAsync(cst, seed_xy, (size_t)2 * n * sizeof(float), hipMemcpyHostToDevice, st));
   else
     TVL1_TRY(shift_chunks(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, W, H, R, shifts,
                           cst, st));
-  const Seed seed{plane_b ? reinterpret_cast<float *>(c->seed_scratch + cst_b) : nullptr,
-                  plane_b ? reinterpret_cast<float *>(c->seed_scratch + cst_b + plane_b) : nullptr,
+  const Seed seed{plane_b ? c->seed_scratch.as<float>(cst_b) : nullptr,
+                  plane_b ? c->seed_scratch.as<float>(cst_b + plane_b) : nullptr,
                   (size_t)W, 0, cst};
   s = calc_batch(c, n, I0, pitch0, pair_stride0, I1, pitch1, pair_stride1, &seed, W, H, u, v, fpitch,
                  flow_pair_stride, stats, stream);
@@ -3094,7 +2923,7 @@ static tvl1_status calc_host(tvl1_ctx *c, const uint8_t *I0, size_t pitch0, cons
   tvl1_status s = check_call(c, I0, pitch0, I1, pitch1, W, H, u, v, fpitch);
   if (s != TVL1_OK) return s;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t st = c->own_stream;
+  hipStream_t st = c->mem.own;
   s = ensure_geometry(c, W, H, st);
   if (s != TVL1_OK) return s;
   const size_t P0 = (size_t)c->geo.ps[0];
@@ -3168,15 +2997,11 @@ tvl1_status tvl1_gather_flow(tvl1_ctx *c, const float *u, const float *v, int64_
                      (long long)offsets[i], i, (long long)plane_elems);
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
-  order_streams(c, st);
-  const size_t need = align_up((size_t)n * sizeof(int64_t), 256) + (size_t)n * sizeof(float2);
-  if (need > c->gather_bytes) {
-    const tvl1_status r = arena_alloc(c, &c->gather_scratch, &c->gather_bytes,
-                                      std::max<size_t>(need, 64 << 10), st);
-    if (r != TVL1_OK) return r;
-  }
-  int64_t *doff = reinterpret_cast<int64_t *>(c->gather_scratch);
-  float2 *dout = reinterpret_cast<float2 *>(c->gather_scratch + align_up((size_t)n * sizeof(int64_t), 256));
+  c->mem.enter(st);
+  const size_t off_b = align_up((size_t)n * sizeof(int64_t), 256);
+  TVL1_TRY(reserve(c, c->gather_scratch, off_b + (size_t)n * sizeof(float2), st, 64 << 10));
+  int64_t *doff = c->gather_scratch.as<int64_t>();
+  float2 *dout = c->gather_scratch.as<float2>(off_b);
   std::vector<float2> host((size_t)n);
   HIP_TRY(c, hipMemcpyAsync(doff, offsets, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_gather_flow, dim3((n + 255) / 256), dim3(256), 0, st, u, v, doff, n, dout);
@@ -3233,13 +3058,12 @@ static tvl1_status run_chunks(tvl1_ctx *c, void *stream, int32_t n, double bytes
   hipStream_t st = (hipStream_t)stream;
   unsigned long long *cnt = nullptr;
   if (counts) {
-    order_streams(c, st);
-    if (!c->retired.empty()) reap_retired(c, false);
+    c->mem.enter(st);
     const size_t need = kFbChunk * sizeof(tvl1_invert_counts);   // the largest record
-    if (need > c->count_bytes) TVL1_TRY(arena_alloc(c, &c->count_scratch, &c->count_bytes, need, st));
-    cnt = reinterpret_cast<unsigned long long *>(c->count_scratch);
+    TVL1_TRY(reserve(c, c->count_scratch, need, st));
+    cnt = c->count_scratch.as<unsigned long long>();
   }
-  const size_t tok = xprof_begin(c, st);
+  const size_t tok = c->xprof.begin(c->profiling, st);
   for (int32_t b = 0; b < n; b += kFbChunk) {
     const int m = std::min(kFbChunk, n - b);
     // the next chunk's zero fill is in stream order behind this one's copy
@@ -3249,7 +3073,7 @@ static tvl1_status run_chunks(tvl1_ctx *c, void *stream, int32_t n, double bytes
       HIP_TRY(c, hipMemcpyAsync(pair_at(static_cast<char *>(counts), b, rec), cnt, (size_t)m * rec,
                                 hipMemcpyDeviceToHost, st));
   }
-  xprof_end(c, st, tok, bytes);
+  c->xprof.end(st, tok, 2,bytes);
   HIP_TRY(c, hipGetLastError());
   if (cnt) HIP_TRY(c, hipStreamSynchronize(st));
   return TVL1_OK;
@@ -3471,43 +3295,30 @@ tvl1_status tvl1_warp_by_flow_u8(tvl1_ctx *c, const uint8_t *I1, size_t pitch1, 
   });
 }
 
-void *tvl1_stream(tvl1_ctx *c) { return c ? (void *)c->own_stream : nullptr; }
+void *tvl1_stream(tvl1_ctx *c) { return c ? (void *)c->mem.own : nullptr; }
 
 tvl1_status tvl1_set_profiling(tvl1_ctx *c, int32_t enable) {
   if (!c) return set_err(nullptr, TVL1_EINVAL, "ctx is NULL");
   c->profiling = enable != 0;
-  if (!c->profiling) {   // slice-list marks still waiting for a solve do not outlive the switch
-    c->xmarks.clear();
-    c->xev_used = 0;
-  }
+  if (!c->profiling) c->xprof.reset();   // marks still waiting for a solve do not outlive the switch
   return TVL1_OK;
 }
 
 void tvl1_destroy(tvl1_ctx *c) {
   if (!c) return;
-  for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->xev_pool) (void)hipEventDestroy(e);
+  c->prof.destroy();
+  c->xprof.destroy();
   (void)hipSetDevice(c->device);
-  if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
+  if (c->mem.own) (void)hipStreamSynchronize(c->mem.own);
   // hipFree waits for the device: callers' streams included
-  if (c->arena) (void)hipFree(c->arena);
-  if (c->barena) (void)hipFree(c->barena);
-  if (c->align_scratch) (void)hipFree(c->align_scratch);
-  if (c->map_scratch) (void)hipFree(c->map_scratch);
-  if (c->gather_scratch) (void)hipFree(c->gather_scratch);
-  if (c->small_scratch) (void)hipFree(c->small_scratch);
-  if (c->shift_scratch) (void)hipFree(c->shift_scratch);
-  if (c->seed_scratch) (void)hipFree(c->seed_scratch);
-  if (c->count_scratch) (void)hipFree(c->count_scratch);
-  for (auto &r : c->retired) free_retired(r);
+  c->mem.release_all(c->arena, c->barena, c->align_scratch, c->map_scratch, c->gather_scratch,
+                     c->small_scratch, c->shift_scratch, c->seed_scratch, c->count_scratch);
   if (c->align_pat) (void)hipFree(c->align_pat);
   if (c->pinned) (void)hipHostFree(c->pinned);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  if (c->mem.own) (void)hipStreamDestroy(c->mem.own);
   for (hipEvent_t e : c->ev_check)
     if (e) (void)hipEventDestroy(e);
   if (c->gate) (void)hipFree(c->gate);
-  if (c->ev_order) (void)hipEventDestroy(c->ev_order);
-  if (c->ev_switch) (void)hipEventDestroy(c->ev_switch);
   delete c;
 }
 

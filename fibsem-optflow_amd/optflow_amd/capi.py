@@ -558,7 +558,7 @@ class Engine:
         self._check(rc, "tvl1_find_alignment")
         return np.array(list(aff), np.float32).reshape(2, 3), int(ng.value), int(oc.value)
 
-    def orb_detect(self, d: int, pitch: int, w: int, h: int, cap: int = 10000, **kw):
+    def orb_detect(self, d: int, pitch: int, w: int, h: int, cap: int = 10000, stream: int = 0, **kw):
         """tvl1_orb_detect on a device frame -> (kp (n, 5): x, y, octave, angle, response;
         desc (n, 32) u8)."""
         ap = align_params(self.lib, **kw)
@@ -567,7 +567,7 @@ class Engine:
         n = C.c_int32(0)
         self._check(self.lib.tvl1_orb_detect(self.ctx, C.c_void_p(d), pitch, w, h, C.byref(ap),
                                              kp.ctypes.data, desc.ctypes.data, cap, C.byref(n),
-                                             None), "tvl1_orb_detect")
+                                             C.c_void_p(stream) if stream else None), "tvl1_orb_detect")
         m = min(n.value, cap)
         return kp[:m], desc[:m]
 
